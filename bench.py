@@ -36,9 +36,24 @@ duckdb_mb_arrow_row_count), checked row for row against the oracle.
 --groups (1e5) dense INT64 keys (F3, partitioned in LDS); c3s over sparse keys
 (F3h, hashed partitions).
 
+A plain run does only what the headline needs: set-up, warmup, the K timed
+steps (with the kernel's HIP events, which the timed loop records anyway) and
+the result line.  --full adds everything else the benchmark measures or checks,
+each in runs of its own after the timed loop: parity against the CPU oracle at
+full size, the measured HBM ceilings, the "extra" sub-benchmarks, the RCCL
+self-test, the multi-device legs (other combine, 1 -> N curve, overhead split)
+and the CPU baseline.
+
+--dump-outputs DIR writes what the last timed step returned to its caller as
+DIR/<name>.npy (float64): the result cells of the query (GROUP BY rows sorted by
+key, NULL key last, as SQL leaves their order open); for sel the row count and
+a fixed, seeded sample of slices of the compacted column.  The column is
+generated from fixed seeds, so two builds run with the same arguments see the
+same inputs.
+
 Usage: python bench.py [--gpus N] [--shards-per-gpu S] [--ranks] [--steps K] [--warmup W]
                        [--rows R] [--config c1|c2|c2d|c3|c3n|c3h|c3s|c4|c5|sel] [--groups G]
-                       [--extra c3,sel,c3n,c3h,c3s] [--no-cpu]
+                       [--full [--extra c3,sel,c3n,c3h,c3s] [--no-cpu]] [--dump-outputs DIR]
 """
 import argparse
 import json
@@ -98,6 +113,12 @@ def main():
     ap.add_argument("--extra", default="auto",
                     help="comma-separated sub-benchmarks (c3, sel, c3n, c3h, c3s) reported under the headline "
                          "line's \"extra\" key; auto = all five for the 1-GPU C2 line, none otherwise")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: oracle parity at full size, measured "
+                         "HBM ceilings, the --extra sub-benchmarks, the RCCL self-test, the multi-device legs "
+                         "and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float64)")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     ap.add_argument("--dry-run", action="store_true",
@@ -106,6 +127,10 @@ def main():
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                     help="--ranks only: nccl (= RCCL over xGMI) for real runs; gloo to rehearse N>1 on fewer GPUs")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full and args.extra not in ("auto", ""):
+        ap.error("--extra sub-benchmarks run under --full")
     if args.rows is None:
         args.rows = 1_250_000_000 if args.config == "c5" else 1_000_000_000
 
@@ -524,7 +549,7 @@ def run_inlib(args, world, rank, vote=None):
     import torch
     mbx = load_mbx()
     selftest = None
-    if plan["ngpu"] > 1:
+    if args.full and plan["ngpu"] > 1:
         # the RCCL calls of the combine over every GPU of the run, before any
         # table exists: a fresh ncclCommInitAll over devices 0..N-1 and the
         # multi-rank reduce / all-gather check, with what RCCL reports per rank
@@ -580,12 +605,15 @@ def run_inlib(args, world, rank, vote=None):
         elapsed = float(t_all.item())
     threads = len(os.sched_getaffinity(0))
     shard_par = None
-    log("[bench] parity check against the oracle")
-    if sstats and args.config in ("c2", "c2d", "c5", "c3"):
+    if not args.full:
+        parity = dict(PARITY_NOT_RUN)
+    elif sstats and args.config in ("c2", "c2d", "c5", "c3"):
+        log("[bench] parity check against the oracle")
         parity, shard_par = sharded_parity(conn, args.config, out, n_total, plan["nshards"], threads)
     else:
+        log("[bench] parity check against the oracle")
         parity, _ = parity_check(conn, args.config, w["sql"], out, 0, n_total, threads, args.groups)
-    if sstats:
+    if sstats and args.full:
         parity["checked"] = (f"the global answer over all {n_total} rows ({plan['nshards']} shards, merged in the "
                              f"library) vs the oracle over the same rows"
                              + ("; every shard's partial vs the oracle over its own row range" if shard_par else ""))
@@ -609,7 +637,8 @@ def run_inlib(args, world, rank, vote=None):
             "peer_links": sstats["peer_links"], "host_results": sstats["host_results"],
             "note": ("shards on one device run concurrently, so per-launch times overlap"
                      if plan["shards_per_gpu"] > 1 else "one shard per device")}
-        md["split_us"] = overhead_split(conn, step, 10)
+        if args.full:
+            md["split_us"] = overhead_split(conn, step, 10)
         if shard_par is not None:
             md["shard_parity"] = [{k: v for k, v in e.items() if k != "oracle"} for e in shard_par]
         # the timed loop ran the library's default combine (RCCL over the shard
@@ -619,7 +648,7 @@ def run_inlib(args, world, rank, vote=None):
                          "rccl": rccl_evidence(conn.rccl_info(), plan["devices"])}
         if selftest is not None:
             md["rccl_selftest"] = selftest
-        if args.config in ("c2", "c2d", "c5", "c3"):
+        if args.full and args.config in ("c2", "c2d", "c5", "c3"):
             # the other mode, timed right after
             md["combine_ab"] = guarded(
                 lambda: combine_leg(conn, step, args, n_total, "host" if cb_out["ran_rccl_steps"] else "rccl"),
@@ -630,7 +659,8 @@ def run_inlib(args, world, rank, vote=None):
             # prefixes 1, 2, 4 ... of 0..N-1, each its own connection and table
             md["curve"] = guarded(lambda: curve_legs(mbx, args, plan, result, shard_par), CURVE_TIMEOUT_S)
         result["multi_device"] = md
-    calibrate_into(conn, result, args.config)
+    if args.full:
+        calibrate_into(conn, result, args.config)
     if args.config == "sel":
         # every timed step must have run the one-pass kernel (per shard): a fallback fails parity loudly
         result["select_rounds"] = sr_out
@@ -638,7 +668,7 @@ def run_inlib(args, world, rank, vote=None):
         if sr_out["fallbacks"] or sr_out["select_rounds_launches"] < args.steps * plan["nshards"]:
             result["parity"]["match"] = False
             result["parity"]["fallback_error"] = f"select_rounds outcomes in the timed loop: {sr_out}"
-    extras = args.extra
+    extras = args.extra if args.full else ""
     if extras == "auto":
         extras = "c3,sel,c3n,c3h,c3s" if (args.config == "c2" and plan["nshards"] == 1) else ""
     if extras:
@@ -660,8 +690,9 @@ def run_inlib(args, world, rank, vote=None):
             result["extra"]["rccl_selftest"] = mbx.rccl_selftest([0])
         except Exception as ex:  # noqa: BLE001
             result["extra"]["rccl_selftest"] = {"ok": False, "error": str(ex)}
-    log("[bench] parity done")
-    if not args.no_cpu and plan["nshards"] == 1 and args.config in ("c2", "c2d", "c3", "c3n", "c3h", "c3s", "c5", "sel"):
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, args.config, out, conn, w["sql"])
+    if args.full and not args.no_cpu and plan["nshards"] == 1 and args.config in ("c2", "c2d", "c3", "c3n", "c3h", "c3s", "c5", "sel"):
         result["cpu_baseline"] = cpu_baseline(args.cpu_seconds,
                                               {"c2d": "c2", "c3n": "c3", "c3s": "c3h"}.get(args.config, args.config),
                                               args.groups)
@@ -671,7 +702,7 @@ def run_inlib(args, world, rank, vote=None):
     if not stuck:
         conn.close()
     print(json.dumps(result), flush=True)
-    bad = not result["parity"].get("match", True) or (shard_par and not all(p["match"] for p in shard_par))
+    bad = result["parity"].get("match") is False or (shard_par and not all(p["match"] for p in shard_par))
     if bad:
         log("[bench] PARITY FAILURE: " + json.dumps(result["parity"]) +
             (" shards: " + json.dumps([p for p in shard_par if not p["match"]]) if shard_par else ""))
@@ -1053,6 +1084,55 @@ def headline(args, w, ngpu, elapsed, avg_kernel_ms, n_rows_step, launch_rows, pa
     }
 
 
+PARITY_NOT_RUN = {"match": None, "checked": "not checked: --full compares the answer with the CPU oracle at full size"}
+DUMP_SEL_SLICES = 4          # sel: slices of the compacted column kept by --dump-outputs ...
+DUMP_SEL_SLICE_ROWS = 1_000_000  # ... of this many rows each (32 MB as float64)
+DUMP_SEED = 20240531
+
+
+def output_arrays(config, out):
+    """The last timed step's return value as named float64 arrays: what a
+    caller of the query receives, cell for cell."""
+    import numpy as np
+    if config in ("c3", "c3n", "c3h", "c3s"):
+        # (key or None, COUNT, SUM or None) per group; NULL -> NaN
+        rows = sorted(decode_c3(out), key=lambda g: (g[0] is None, g[0] if g[0] is not None else 0))
+        f = lambda v: float("nan") if v is None else float(v)  # noqa: E731
+        return {"k": np.array([f(g[0]) for g in rows], dtype=np.float64),
+                "sum_v": np.array([f(g[2]) for g in rows], dtype=np.float64),
+                "count_star": np.array([f(g[1]) for g in rows], dtype=np.float64)}
+    if config == "sel":
+        return {"row_count": np.array([float(out[0])], dtype=np.float64)}
+    names = ["count_star", "sum_x"]
+    return {names[i]: np.array([float("nan") if v is None else float(int(v))], dtype=np.float64)
+            for i, v in enumerate(out)}
+
+
+def dump_outputs(d, config, out, conn, sql):
+    """--dump-outputs: output_arrays() as d/<name>.npy; for sel also a seeded
+    sample of slices of the result column, read as the parity check reads it."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    arrs = output_arrays(config, out)
+    if config == "sel":
+        rows = int(out[0])
+        nsl = max(1, -(-rows // DUMP_SEL_SLICE_ROWS))
+        rng = np.random.default_rng(DUMP_SEED)
+        picks = sorted(int(x) for x in rng.choice(nsl, size=min(DUMP_SEL_SLICES, nsl), replace=False))
+        parts = []
+        for k in picks:
+            a = conn.query_arrow(f"{sql} LIMIT {DUMP_SEL_SLICE_ROWS} OFFSET {k * DUMP_SEL_SLICE_ROWS}").value
+            raw = a.raw_int64_bytes(0)
+            a.close()
+            cnt = int.from_bytes(raw[:4], "little", signed=True)
+            parts.append(np.frombuffer(raw, dtype=np.int64, offset=4, count=cnt).astype(np.float64))
+        arrs["x_sample"] = np.concatenate(parts) if parts else np.zeros(0, dtype=np.float64)
+        arrs["x_sample_offsets"] = np.array([k * DUMP_SEL_SLICE_ROWS for k in picks], dtype=np.float64)
+    for name, a in arrs.items():
+        np.save(os.path.join(d, name + ".npy"), a)
+    log(f"[bench] outputs written to {d}: " + ", ".join(f"{n}{list(a.shape)}" for n, a in arrs.items()))
+
+
 def calibrate_into(conn, result, config):
     """This box's measured ceilings beside the spec peak; outside the timed loop."""
     achieved = result["roofline"]["achieved"]
@@ -1233,8 +1313,11 @@ def run_ranks(args, world, rank, local_rank, vote=None):
     if world > 1:
         dist.all_reduce(t_all, op=dist.ReduceOp.MAX)  # (gloo world group)
     elapsed = float(t_all.item())
-    parity, orc = parity_check(conn, args.config, w["sql"], out, start, n, host_share(world))
-    if world > 1 and args.config in ("c2", "c2d", "c5"):
+    if args.full:
+        parity, orc = parity_check(conn, args.config, w["sql"], out, start, n, host_share(world))
+    else:
+        parity, orc = dict(PARITY_NOT_RUN), None
+    if args.full and world > 1 and args.config in ("c2", "c2d", "c5"):
         # global answer (combined over RCCL in the timed loop) vs the sum of the shard oracles
         g_oracle, g_osum = mbx_dist.global_count_sum(orc[0], orc[1], device=coll_dev, group=group)
         parity["global_count"] = gcount
@@ -1244,7 +1327,7 @@ def run_ranks(args, world, rank, local_rank, vote=None):
             parity["global_sum"] = gsum
             parity["global_oracle_sum"] = g_osum
             parity["match"] = parity["match"] and gsum == g_osum
-    if world > 1 and args.config == "c3":
+    if args.full and world > 1 and args.config == "c3":
         g_exp = mbx_dist.global_group_count_sum(orc, device=coll_dev, group=group)
         parity["global_groups"] = len(ggroups)
         parity["global_oracle_groups"] = len(g_exp)
@@ -1270,8 +1353,11 @@ def run_ranks(args, world, rank, local_rank, vote=None):
             result["multi_device"] = {"path": "one process per GPU (torch.distributed)", "ranks": world,
                                       "combine": ("RCCL (nccl group)" if args.dist_backend == "nccl" else "gloo"),
                                       "per_rank": per_rank}
-        calibrate_into(conn, result, args.config)
-        if not args.no_cpu and world == 1 and args.config in ("c2", "c2d", "c3", "c5", "sel"):
+        if args.full:
+            calibrate_into(conn, result, args.config)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, args.config, out, conn, w["sql"])
+        if args.full and not args.no_cpu and world == 1 and args.config in ("c2", "c2d", "c3", "c5", "sel"):
             result["cpu_baseline"] = cpu_baseline(args.cpu_seconds, "c2" if args.config == "c2d" else args.config)
     if world > 1:
         dist.barrier()
@@ -1279,7 +1365,7 @@ def run_ranks(args, world, rank, local_rank, vote=None):
     conn.close()
     if rank == 0:
         print(json.dumps(result), flush=True)
-        if not result["parity"].get("match", True) or not all(p["shard_match"] for p in per_rank):
+        if result["parity"].get("match") is False or any(p["shard_match"] is False for p in per_rank):
             log("[bench] PARITY FAILURE: " + json.dumps(per_rank))
             raise SystemExit(3)
 

@@ -350,3 +350,39 @@ def test_curve_legs_schema_and_parity_on_cpu(config, monkeypatch):
             assert p["parity"]["match"] == (wrong is None or p["shards"] == 1), p
         assert pts[0]["speedup_vs_1"] == 1.0
         assert [len(c.devices) for c in made] == [1, 2, 4]
+
+
+def test_output_arrays_are_the_callers_cells():
+    """--dump-outputs: the last step's result cells as float64 arrays; GROUP BY
+    rows sorted by key with the NULL key last and NULL cells as NaN."""
+    import numpy as np
+    import bench
+    a = bench.output_arrays("c2", ["520001011"])
+    assert list(a) == ["count_star"] and a["count_star"].dtype == np.float64 and a["count_star"].tolist() == [520001011.0]
+    a = bench.output_arrays("c5", ["7", "-12"])
+    assert a["count_star"].tolist() == [7.0] and a["sum_x"].tolist() == [-12.0]
+    cells = ("c3cells", [["", "5", "2"], ["3", "", "1"], ["1", "40", "4"]],
+             [[True, False], [False, True], [False, False]])
+    a = bench.output_arrays("c3n", cells)
+    assert a["k"].tolist()[:2] == [1.0, 3.0] and np.isnan(a["k"][2])
+    assert a["count_star"].tolist() == [4.0, 1.0, 2.0]
+    assert a["sum_v"][0] == 40.0 and np.isnan(a["sum_v"][1]) and a["sum_v"][2] == 5.0
+    assert all(v.dtype == np.float64 for v in a.values())
+
+
+def test_dump_outputs_writes_npy(tmp_path):
+    import numpy as np
+    import bench
+    d = tmp_path / "dump"
+    bench.dump_outputs(str(d), "c2", ["42"], None, "")
+    assert sorted(os.listdir(d)) == ["count_star.npy"]
+    assert np.load(d / "count_star.npy").tolist() == [42.0]
+
+
+def test_extra_needs_full():
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--extra", "c3", "--dry-run"],
+                       capture_output=True, text=True, timeout=120, env=_bare_env())
+    assert p.returncode == 2 and "--full" in p.stderr
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--extra", "c3", "--dry-run"],
+                       capture_output=True, text=True, timeout=120, env=_bare_env())
+    assert p.returncode == 0, p.stderr[-2000:]
