@@ -4,6 +4,7 @@
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>
 
+#include "group_code.h"
 #include "vm.h"
 
 namespace mbx {
@@ -153,6 +154,10 @@ struct PartGroupDesc {
   const void *key;
   int kphys;
   int64_t kmin, range;
+  // composite / NULL-able keys: the rows' key is the group code of this plan
+  // (group_code.h), computed in the hist and scatter passes; key / kphys are
+  // unused, kmin = 0 and range = the plan's total on the dense path
+  const GroupCodePlan *code;
   const void *v0, *v1;
   int vphys, nv;
   bool mm;
@@ -280,6 +285,10 @@ struct EmitDesc {
     int32_t phys, nullable;
     int64_t kmin, radix, stride;
   } kc[EMIT_MAX_CKEYS];
+  // composite keys out of a hashed table (the partitioned GROUP BY over group
+  // codes): the code of slot sl is code_msb[sl] ^ 2^63 instead of sl itself
+  const unsigned long long *code_msb;
+  static_assert(kGroupCodeMaxKeys <= EMIT_MAX_CKEYS, "a group-code plan's keys must fit EmitDesc::kc");
   // optional: reduce these per-workgroup partials into slot 0 first
   // (states of every aggregate and cstar[0]); emit then runs one workgroup
   const AggPartial *partials;

@@ -2109,103 +2109,16 @@ static bool CountMayStayOnDevice(const Engine &e, const BoundSelect &s) {
   return true;
 }
 
-// F3h: the wide GROUP BY over hashed partitions (group_part.hip); groups come
-// out in hash-table order (DuckDB's hash aggregate order is unspecified too).
-// false: a table filled up (more groups than the tables hold) -- the caller's
-// hash path answers.
-static bool PartGroupHashedAggregate(Engine &e, const DRel &src, const BoundSelect &s, const DCol &K,
-                                     const std::vector<int> &vcols, bool mm, i128 maxabs, DRel &out) {
-  const int na = (int)s.aggs.size(), nv = (int)vcols.size();
-  const int64_t nslots = dev::PartGroupHashedSlots();
-  size_t hb = 0, sb = 0, rb = 0, cb = 0;
-  dev::PartGroupHashedScratch(src.n, nv, &hb, &sb, &rb, &cb);
-  auto cs = Alloc(e, nslots * 8);
-  auto stb = Alloc(e, (size_t)nslots * sizeof(dev::AggState));
-  auto gk = Alloc(e, nslots * 8);
-  auto hist = Alloc(e, hb), startb = Alloc(e, sb), rows = Alloc(e, rb), scan = Alloc(e, cb);
-  dev::PartGroupDesc d;
-  memset(&d, 0, sizeof(d));
-  d.key = K.data;
-  d.kphys = K.phys;
-  d.v0 = nv > 0 ? src.cols[vcols[0]].data : nullptr;
-  d.vphys = nv ? src.cols[vcols[0]].phys : P_I64;
-  d.nv = nv;
-  d.mm = mm;
-  d.n = src.n;
-  d.vmaxabs = nv ? (uint64_t)std::max<i128>(maxabs, 1) : 0;
-  d.cstar = (unsigned long long *)cs->p;
-  d.st0 = (dev::AggState *)stb->p;
-  d.scratch_hist = hist->p, d.scratch_start = startb->p, d.scratch_rows = rows->p, d.scratch_scan = scan->p;
-  d.scratch_scan_bytes = cb;
-  int32_t *ovf = (int32_t *)((char *)e.d_small + 3584);
-  double bytes = (double)src.n * PhysSize(K.phys) + (nv ? (double)src.n * PhysSize((Phys)d.vphys) : 0);
-  {
-    ProfScope ps(e, "group_part_hashed", bytes, src.n);
-    if (!dev::PartGroupHashed(d, (unsigned long long *)gk->p, ovf, e.stream)) {
-      if (Knob("MBX_PG_DEBUG")) fprintf(stderr, "[mbx] F3h: launch refused\n");
-      return false;
-    }
-  }
-  if (const int32_t o = ReadDev<int32_t>(e, ovf)) {  // more groups than the tables hold
-    if (Knob("MBX_PG_DEBUG")) fprintf(stderr, "[mbx] F3h: table overflow flag %d\n", o);
-    return false;
-  }
-  auto list = Alloc(e, nslots * 4);
-  const bool defer = CountMayStayOnDevice(e, s);
-  DevBufPtr nbuf = defer ? Alloc(e, 8) : nullptr;
-  int64_t *const n_out = defer ? (int64_t *)nbuf->p : e.d_scratch;
-  dev::CompactSlots((const unsigned long long *)cs->p, nslots, (int32_t *)list->p, n_out, e.stream);
-  dev::EmitDesc D;
-  memset(&D, 0, sizeof(D));
-  D.nagg = na;
-  D.cstar = (const unsigned long long *)cs->p;
-  D.slot_list = (const int32_t *)list->p;
-  D.n_list = n_out;
-  D.nslots = nslots;
-  D.has_key = 1;
-  D.key_phys = PhysOf(s.groups[0]->type);
-  D.key_msb = (const unsigned long long *)gk->p;
-  D.null_slot = -1;
-  DCol kc = AllocOut(e, s.groups[0]->type, nslots, true, false);
-  D.key_out = kc.data;
-  D.key_valid = (uint32_t *)kc.validity;
-  out.cols.clear();
-  out.cols.push_back(kc);
-  for (int j = 0; j < na; j++) {
-    DCol oc = AllocOut(e, s.aggs[j].type, nslots, true, false);
-    D.a[j] = EmitFor(s.aggs[j], VC_I64, s.aggs[j].kind == A_COUNT_STAR ? nullptr : d.st0, oc);
-    out.cols.push_back(oc);
-  }
-  dev::EmitAggRelation(D, e.stream);
-  if (defer) {
-    out.n = nslots;
-    out.n_dev = n_out;
-    out.n_owner = nbuf;
-  } else {
-    out.n = ReadDev<int64_t>(e, n_out);
-  }
-  return true;
-}
-
-// F3: GROUP BY one integer key (no NULLs) whose zone-map range is too wide for
-// F2's LDS tables but dense enough for per-key state arrays (1024 < range <=
-// PartGroupMaxRange, range <= 4 n), no WHERE, COUNT / SUM / MIN / MAX / AVG over
-// <= 2 integer columns of one phys without NULLs: rows partitioned by key
-// range, each partition reduced in LDS (group_part.hip), then the non-empty
-// keys compacted and emitted in key order as F2 does.  false: the shape does
-// not fit (the hash path or the run-time compiled kernel takes it).
-static bool PartGroupAggregate(Engine &e, const DRel &src, const BoundSelect &s, DRel &out) {
-  const int na = (int)s.aggs.size();
-  if (const char *k = Knob("MBX_PART_GROUP"))  // MBX_PART_GROUP=0: the hash path (A/B)
-    if (atoi(k) == 0) return false;
-  if (s.groups.size() != 1 || s.where || src.range || src.n <= 0 || src.n >= ((int64_t)1 << 32)) return false;
-  if (s.groups[0]->kind != BExpr::COL || !FastIntCol(src, s.groups[0]->col)) return false;
-  const DCol &K = src.cols[s.groups[0]->col];
-  const DevColumn *ks = K.table_col;
-  if (!ks || !ks->stats_valid || ks->null_count != 0) return false;
-  const i128 range = ks->imax - ks->imin + 1;
+// ---- the partitioned GROUP BY (group_part.hip): F3 (dense), F3h (hashed), and
+// both over the group code of composite / NULL-able keys.  The shared parts:
+// The value columns of the shape: COUNT / SUM / MIN / MAX / AVG over <= 2
+// integer columns of one phys without NULLs, zone maps bounding |v| < 2^62.
+struct PartGroupValues {
   std::vector<int> vcols;
   bool mm = false;
+  i128 maxabs = 0;
+};
+static bool PartGroupValueCols(const DRel &src, const BoundSelect &s, PartGroupValues &v) {
   for (auto &a : s.aggs) {
     if (a.kind == A_COUNT_STAR) continue;
     if (a.distinct) return false;
@@ -2213,80 +2126,84 @@ static bool PartGroupAggregate(Engine &e, const DRel &src, const BoundSelect &s,
     if (!x || x->kind != BExpr::COL || !FastIntCol(src, x->col) || a.arg->type.id == T_DOUBLE ||
         a.arg->type.id == T_FLOAT)
       return false;
-    if (a.kind == A_MIN || a.kind == A_MAX) mm = true;
-    if (std::find(vcols.begin(), vcols.end(), x->col) == vcols.end()) vcols.push_back(x->col);
+    if (a.kind == A_MIN || a.kind == A_MAX) v.mm = true;
+    if (std::find(v.vcols.begin(), v.vcols.end(), x->col) == v.vcols.end()) v.vcols.push_back(x->col);
   }
-  const int nv = (int)vcols.size();
-  if (nv > 2 || (nv == 2 && src.cols[vcols[0]].phys != src.cols[vcols[1]].phys)) return false;
-  if (range <= 1024) return false;
-  i128 maxabs = 0;
-  for (int c : vcols) {
+  const int nv = (int)v.vcols.size();
+  if (nv > 2 || (nv == 2 && src.cols[v.vcols[0]].phys != src.cols[v.vcols[1]].phys)) return false;
+  for (int c : v.vcols) {
     const DevColumn *vs = src.cols[c].table_col;
     if (!vs || !vs->stats_valid) return false;
-    maxabs = std::max(maxabs, std::max(vs->imax < 0 ? -vs->imax : vs->imax, vs->imin < 0 ? -vs->imin : vs->imin));
+    v.maxabs = std::max(v.maxabs, std::max(vs->imax < 0 ? -vs->imax : vs->imax, vs->imin < 0 ? -vs->imin : vs->imin));
   }
-  if (maxabs >= ((i128)1 << 62)) return false;
-  // keys too sparse for dense per-key states: hashed partitions (F3h), from
-  // 2^16 rows (below, the hash path's table is small) with at most one value column
-  if (range > dev::PartGroupMaxRange(nv, mm) || range > 4 * (i128)src.n)
-    return nv <= 1 && src.n >= ((int64_t)1 << 16) && PartGroupHashedAggregate(e, src, s, K, vcols, mm, maxabs, out);
-  const int64_t nslots = (int64_t)range;
-  const Phys vphys = nv ? src.cols[vcols[0]].phys : P_I64;
-  size_t hb = 0, sb = 0, rb = 0, cb = 0;
-  dev::PartGroupScratch(src.n, nslots, nv, mm, vphys, &hb, &sb, &rb, &cb);
-  auto cs = Alloc(e, nslots * 8);
-  auto stb = Alloc(e, (size_t)(nv >= 2 ? 2 : 1) * nslots * sizeof(dev::AggState));
-  auto hist = Alloc(e, hb), startb = Alloc(e, sb), rows = Alloc(e, rb), scan = Alloc(e, cb);
+  return v.maxabs < ((i128)1 << 62);
+}
+
+// The run's buffers (count and states per slot, the hashed tables' keys, the
+// passes' scratch) and its descriptor, all but the key fields.
+struct PartGroupRun {
+  DevBufPtr cs, stb, gk, hist, startb, rows, scan;
   dev::PartGroupDesc d;
+  int64_t nslots = 0;
+};
+static void PartGroupPrepare(Engine &e, const DRel &src, const PartGroupValues &v, int64_t dense_range,
+                             PartGroupRun &r) {
+  const int nv = (int)v.vcols.size();
+  const bool hashed = dense_range <= 0;
+  const Phys vphys = nv ? src.cols[v.vcols[0]].phys : P_I64;
+  r.nslots = hashed ? dev::PartGroupHashedSlots() : dense_range;
+  size_t hb = 0, sb = 0, rb = 0, cb = 0;
+  if (hashed) dev::PartGroupHashedScratch(src.n, nv, &hb, &sb, &rb, &cb);
+  else dev::PartGroupScratch(src.n, r.nslots, nv, v.mm, vphys, &hb, &sb, &rb, &cb);
+  r.cs = Alloc(e, r.nslots * 8);
+  r.stb = Alloc(e, (size_t)(nv >= 2 ? 2 : 1) * r.nslots * sizeof(dev::AggState));
+  if (hashed) r.gk = Alloc(e, r.nslots * 8);
+  r.hist = Alloc(e, hb), r.startb = Alloc(e, sb), r.rows = Alloc(e, rb), r.scan = Alloc(e, cb);
+  dev::PartGroupDesc &d = r.d;
   memset(&d, 0, sizeof(d));
-  d.key = K.data;
-  d.kphys = K.phys;
-  d.kmin = (int64_t)ks->imin;
-  d.range = nslots;
-  d.v0 = nv > 0 ? src.cols[vcols[0]].data : nullptr;
-  d.v1 = nv > 1 ? src.cols[vcols[1]].data : nullptr;
+  d.v0 = nv > 0 ? src.cols[v.vcols[0]].data : nullptr;
+  d.v1 = nv > 1 ? src.cols[v.vcols[1]].data : nullptr;
   d.vphys = vphys;
   d.nv = nv;
-  d.mm = mm;
+  d.mm = v.mm;
   d.n = src.n;
-  d.vmaxabs = nv ? (uint64_t)std::max<i128>(maxabs, 1) : 0;
-  d.cstar = (unsigned long long *)cs->p;
-  d.st0 = (dev::AggState *)stb->p;
-  d.scratch_hist = hist->p, d.scratch_start = startb->p, d.scratch_rows = rows->p, d.scratch_scan = scan->p;
+  d.vmaxabs = nv ? (uint64_t)std::max<i128>(v.maxabs, 1) : 0;
+  d.cstar = (unsigned long long *)r.cs->p;
+  d.st0 = (dev::AggState *)r.stb->p;
+  d.scratch_hist = r.hist->p, d.scratch_start = r.startb->p, d.scratch_rows = r.rows->p, d.scratch_scan = r.scan->p;
   d.scratch_scan_bytes = cb;
-  // algorithmic bytes: the key and value columns once
-  double bytes = (double)src.n * PhysSize(K.phys);
-  for (int c : vcols) bytes += (double)src.n * PhysSize(src.cols[c].phys);
-  {
-    ProfScope ps(e, "group_part", bytes, src.n);
-    if (!dev::PartGroup(d, e.stream)) return false;
-  }
-  dev::AggState *const s0p = d.st0, *const s1p = d.st0 + nslots;
+}
+
+// algorithmic bytes of the value columns
+static double PartGroupValueBytes(const DRel &src, const PartGroupValues &v) {
+  double bytes = 0;
+  for (int c : v.vcols) bytes += (double)src.n * PhysSize(src.cols[c].phys);
+  return bytes;
+}
+
+// The non-empty slots compacted and emitted; D carries the key fields and
+// out.cols the key columns (each allocated for r.nslots rows).  The count stays
+// on the device where the statement allows (CountMayStayOnDevice).
+static void PartGroupEmit(Engine &e, const BoundSelect &s, const PartGroupValues &v, const PartGroupRun &r,
+                          dev::EmitDesc &D, DRel &out) {
+  const int na = (int)s.aggs.size();
+  const int64_t nslots = r.nslots;
   auto list = Alloc(e, nslots * 4);
   const bool defer = CountMayStayOnDevice(e, s);
   DevBufPtr nbuf = defer ? Alloc(e, 8) : nullptr;
   int64_t *const n_out = defer ? (int64_t *)nbuf->p : e.d_scratch;
-  dev::CompactSlots((const unsigned long long *)cs->p, nslots, (int32_t *)list->p, n_out, e.stream);
-  dev::EmitDesc D;
-  memset(&D, 0, sizeof(D));
+  dev::CompactSlots((const unsigned long long *)r.cs->p, nslots, (int32_t *)list->p, n_out, e.stream);
   D.nagg = na;
-  D.cstar = (const unsigned long long *)cs->p;
+  D.cstar = (const unsigned long long *)r.cs->p;
   D.slot_list = (const int32_t *)list->p;
   D.n_list = n_out;
   D.nslots = nslots;
-  D.has_key = 1;
-  D.key_phys = PhysOf(s.groups[0]->type);
-  D.kmin = (int64_t)ks->imin;
   D.null_slot = -1;
-  DCol kc = AllocOut(e, s.groups[0]->type, nslots, true, false);
-  D.key_out = kc.data;
-  D.key_valid = (uint32_t *)kc.validity;
-  out.cols.clear();
-  out.cols.push_back(kc);
   for (int j = 0; j < na; j++) {
     DCol oc = AllocOut(e, s.aggs[j].type, nslots, true, false);
     dev::AggState *stp = nullptr;
-    if (s.aggs[j].kind != A_COUNT_STAR) stp = StripWidening(s.aggs[j].arg.get())->col == vcols[0] ? s0p : s1p;
+    if (s.aggs[j].kind != A_COUNT_STAR)
+      stp = StripWidening(s.aggs[j].arg.get())->col == v.vcols[0] ? r.d.st0 : r.d.st0 + nslots;
     D.a[j] = EmitFor(s.aggs[j], VC_I64, stp, oc);
     out.cols.push_back(oc);
   }
@@ -2298,6 +2215,174 @@ static bool PartGroupAggregate(Engine &e, const DRel &src, const BoundSelect &s,
   } else {
     out.n = ReadDev<int64_t>(e, n_out);
   }
+}
+
+// The hashed passes over r.d (its key fields set); false: the launch was
+// refused or a table filled up (more groups than the tables hold) -- the
+// caller's hash path answers.
+static bool PartGroupHashedRun(Engine &e, const DRel &src, PartGroupRun &r, double bytes) {
+  int32_t *ovf = (int32_t *)((char *)e.d_small + 3584);
+  {
+    ProfScope ps(e, "group_part_hashed", bytes, src.n);
+    if (!dev::PartGroupHashed(r.d, (unsigned long long *)r.gk->p, ovf, e.stream)) {
+      if (Knob("MBX_PG_DEBUG")) fprintf(stderr, "[mbx] F3h: launch refused\n");
+      return false;
+    }
+  }
+  if (const int32_t o = ReadDev<int32_t>(e, ovf)) {  // more groups than the tables hold
+    if (Knob("MBX_PG_DEBUG")) fprintf(stderr, "[mbx] F3h: table overflow flag %d\n", o);
+    return false;
+  }
+  return true;
+}
+
+// One key column of slot keys (F3: kmin + slot, F3h: the table's key words)
+static void PartGroupOneKeyOut(Engine &e, const BoundSelect &s, const PartGroupRun &r, dev::EmitDesc &D, DRel &out) {
+  D.has_key = 1;
+  D.key_phys = PhysOf(s.groups[0]->type);
+  DCol kc = AllocOut(e, s.groups[0]->type, r.nslots, true, false);
+  D.key_out = kc.data;
+  D.key_valid = (uint32_t *)kc.validity;
+  out.cols.clear();
+  out.cols.push_back(kc);
+}
+
+// F3h: the wide GROUP BY over hashed partitions (group_part.hip); groups come
+// out in hash-table order (DuckDB's hash aggregate order is unspecified too).
+// false: a table filled up (more groups than the tables hold) -- the caller's
+// hash path answers.
+static bool PartGroupHashedAggregate(Engine &e, const DRel &src, const BoundSelect &s, const DCol &K,
+                                     const PartGroupValues &v, DRel &out) {
+  PartGroupRun r;
+  PartGroupPrepare(e, src, v, 0, r);
+  r.d.key = K.data;
+  r.d.kphys = K.phys;
+  if (!PartGroupHashedRun(e, src, r, (double)src.n * PhysSize(K.phys) + PartGroupValueBytes(src, v))) return false;
+  dev::EmitDesc D;
+  memset(&D, 0, sizeof(D));
+  D.key_msb = (const unsigned long long *)r.gk->p;
+  PartGroupOneKeyOut(e, s, r, D, out);
+  PartGroupEmit(e, s, v, r, D, out);
+  return true;
+}
+
+// F3: GROUP BY one integer key (no NULLs) whose zone-map range is too wide for
+// F2's LDS tables but dense enough for per-key state arrays (1024 < range <=
+// PartGroupMaxRange, range <= 4 n), no WHERE, COUNT / SUM / MIN / MAX / AVG over
+// <= 2 integer columns of one phys without NULLs: rows partitioned by key
+// range, each partition reduced in LDS (group_part.hip), then the non-empty
+// keys compacted and emitted in key order as F2 does.  false: the shape does
+// not fit (the hash path or the run-time compiled kernel takes it).
+static bool PartGroupAggregate(Engine &e, const DRel &src, const BoundSelect &s, DRel &out) {
+  if (const char *k = Knob("MBX_PART_GROUP"))  // MBX_PART_GROUP=0: the hash path (A/B)
+    if (atoi(k) == 0) return false;
+  if (s.groups.size() != 1 || s.where || src.range || src.n <= 0 || src.n >= ((int64_t)1 << 32)) return false;
+  if (s.groups[0]->kind != BExpr::COL || !FastIntCol(src, s.groups[0]->col)) return false;
+  const DCol &K = src.cols[s.groups[0]->col];
+  const DevColumn *ks = K.table_col;
+  if (!ks || !ks->stats_valid || ks->null_count != 0) return false;
+  const i128 range = ks->imax - ks->imin + 1;
+  PartGroupValues v;
+  if (!PartGroupValueCols(src, s, v) || range <= 1024) return false;
+  const int nv = (int)v.vcols.size();
+  // keys too sparse for dense per-key states: hashed partitions (F3h), from
+  // 2^16 rows (below, the hash path's table is small) with at most one value column
+  if (range > dev::PartGroupMaxRange(nv, v.mm) || range > 4 * (i128)src.n)
+    return nv <= 1 && src.n >= ((int64_t)1 << 16) && PartGroupHashedAggregate(e, src, s, K, v, out);
+  PartGroupRun r;
+  PartGroupPrepare(e, src, v, (int64_t)range, r);
+  r.d.key = K.data;
+  r.d.kphys = K.phys;
+  r.d.kmin = (int64_t)ks->imin;
+  r.d.range = r.nslots;
+  {
+    // algorithmic bytes: the key and value columns once
+    ProfScope ps(e, "group_part", (double)src.n * PhysSize(K.phys) + PartGroupValueBytes(src, v), src.n);
+    if (!dev::PartGroup(r.d, e.stream)) return false;
+  }
+  dev::EmitDesc D;
+  memset(&D, 0, sizeof(D));
+  D.kmin = (int64_t)ks->imin;
+  PartGroupOneKeyOut(e, s, r, D, out);
+  PartGroupEmit(e, s, v, r, D, out);
+  return true;
+}
+
+// The same over the group code of 1..4 integer key columns and their validity
+// (group_code.h): GROUP BY k1, k2[, k3[, k4]], or one NULL-able key too wide
+// for F2's LDS tables.  No WHERE, at least 2^16 rows, more than 4096 codes (so
+// the shape never competes with F2 or the run-time compiled jit_group); values
+// as F3 / F3h take them.  Dense codes (total <= PartGroupMaxRange and <= 4 n)
+// come out in code order -- key order, NULLs last per key, as F2 and jit_group
+// emit; else hashed partitions, groups in table order (<= 1 value column).
+// false: the shape does not fit or the hashed tables filled up.
+static bool CodeGroupAggregate(Engine &e, const DRel &src, const BoundSelect &s, DRel &out) {
+  const int ng = (int)s.groups.size();
+  if (const char *k = Knob("MBX_PART_GROUP"))
+    if (atoi(k) == 0) return false;
+  if (ng < 1 || ng > kGroupCodeMaxKeys || s.where || src.range || src.n < ((int64_t)1 << 16) ||
+      src.n >= ((int64_t)1 << 32))
+    return false;
+  GroupCodeKeyIn in[kGroupCodeMaxKeys];
+  bool nullable = false;
+  for (int i = 0; i < ng; i++) {
+    const BExpr *x = StripWidening(s.groups[i].get());
+    // integer types only (DECIMAL / DATE keys keep the hash path); the emitted
+    // key column is a fixed-width integer of at most 64 bits
+    if (x->kind != BExpr::COL || !IsIntegral(s.groups[i]->type.id) || !IsIntegral(x->type.id) ||
+        ClassOf(s.groups[i]->type) != VC_I64)
+      return false;
+    const Phys kp = PhysOf(s.groups[i]->type);
+    if (kp == P_I128 || kp == P_U64) return false;
+    const DCol &c = src.cols[x->col];
+    if (!c.table_col || c.table_col->data != c.data) return false;
+    in[i].data = c.data;
+    in[i].validity = c.validity;
+    in[i].phys = c.phys;
+    in[i].stats_valid = c.table_col->stats_valid;
+    in[i].imin = c.table_col->imin;
+    in[i].imax = c.table_col->imax;
+    nullable |= c.validity != nullptr;
+  }
+  if (ng == 1 && !nullable) return false;  // F3's own shape
+  GroupCodePlan plan;
+  if (!PlanGroupCode(in, ng, &plan) || plan.total <= 4096) return false;
+  PartGroupValues v;
+  if (!PartGroupValueCols(src, s, v)) return false;
+  const int nv = (int)v.vcols.size();
+  const bool dense = plan.total <= dev::PartGroupMaxRange(nv, v.mm) && (i128)plan.total <= 4 * (i128)src.n;
+  if (!dense && nv > 1) return false;
+  // algorithmic bytes: every key column, n / 8 per validity bitmap, every value column
+  double bytes = PartGroupValueBytes(src, v);
+  for (int i = 0; i < ng; i++)
+    bytes += (double)src.n * PhysSize((Phys)in[i].phys) + (in[i].validity ? (double)src.n / 8 : 0);
+  PartGroupRun r;
+  PartGroupPrepare(e, src, v, dense ? plan.total : 0, r);
+  r.d.code = &plan;
+  if (dense) {
+    r.d.range = plan.total;
+    ProfScope ps(e, "group_part", bytes, src.n);
+    if (!dev::PartGroup(r.d, e.stream)) return false;
+  } else if (!PartGroupHashedRun(e, src, r, bytes)) {
+    return false;
+  }
+  dev::EmitDesc D;
+  memset(&D, 0, sizeof(D));
+  if (!dense) D.code_msb = (const unsigned long long *)r.gk->p;
+  D.nkeys_c = ng;
+  out.cols.clear();
+  for (int i = 0; i < ng; i++) {
+    DCol kc = AllocOut(e, s.groups[i]->type, r.nslots, true, false);
+    D.kc[i].out = kc.data;
+    D.kc[i].valid = (uint32_t *)kc.validity;
+    D.kc[i].phys = PhysOf(s.groups[i]->type);
+    D.kc[i].nullable = plan.k[i].nullable;
+    D.kc[i].kmin = plan.k[i].kmin;
+    D.kc[i].radix = plan.k[i].radix;
+    D.kc[i].stride = plan.k[i].stride;
+    out.cols.push_back(kc);
+  }
+  PartGroupEmit(e, s, v, r, D, out);
   return true;
 }
 
@@ -2587,6 +2672,12 @@ generic:
   if (jit::Enabled()) {
     DRel fused;
     if (ng == 0 ? JitAggregate(e, src, s, fused) : JitGroupAggregate(e, src, s, fused)) return fused;
+  }
+  // ---- composite / NULL-able integer keys over more than 4096 codes: the
+  //      partitioned GROUP BY over the keys' group code
+  if (ng >= 1) {
+    DRel code_out;
+    if (CodeGroupAggregate(e, src, s, code_out)) return code_out;
   }
   DRel tmp = FilterProject(e, src, s.where, exprs);
   if (ng == 0) {

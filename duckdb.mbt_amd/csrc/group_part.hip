@@ -38,6 +38,7 @@
 #include <stdexcept>
 
 #include "device.h"
+#include "group_code.h"
 #include "knobs.h"
 #include "phys.h"
 
@@ -77,6 +78,57 @@ __device__ __forceinline__ int pg_part(int64_t k, int64_t kmin, int shift) {
   return HASHED ? (int)(pg_mix((uint64_t)k) >> (64 - shift)) : (int)((uint64_t)(k - kmin) >> shift);
 }
 
+// Where a row's 64-bit key comes from: one key column (PgCol), or the group
+// code of 1..4 key columns and their validity (PgCode, group_code.h) computed
+// in registers -- no composed key column is written to HBM.
+template <typename TK>
+struct PgCol {
+  static constexpr bool kCode = false;
+  const TK *__restrict__ p;
+  __device__ __forceinline__ int64_t operator()(int64_t r) const { return (int64_t)p[r]; }
+};
+struct PgCode {
+  static constexpr bool kCode = true;
+  GroupCodePlan plan;
+  // codes of N rows, folded column by column (N loads of one column in flight,
+  // then their multiply-adds), in A: uint32_t where total < 2^32 (the dense
+  // path: every digit x stride stays below total), else 64 bits
+  template <typename A, int N>
+  __device__ __forceinline__ void rows(const int64_t (&r)[N], A (&code)[N]) const {
+#pragma unroll
+    for (int u = 0; u < N; u++) code[u] = 0;
+#pragma unroll
+    for (int q = 0; q < kGroupCodeMaxKeys; q++) {
+      if (q >= plan.nkeys) break;  // (uniform)
+      const GroupCodeKey &K = plan.k[q];
+      A dg[N];
+      if (K.phys == P_I64) {
+#pragma unroll
+        for (int u = 0; u < N; u++) dg[u] = (A)((uint64_t)((const int64_t *)K.data)[r[u]] - (uint64_t)K.kmin);
+      } else {
+#pragma unroll
+        for (int u = 0; u < N; u++) dg[u] = (A)((uint64_t)(int64_t)((const int32_t *)K.data)[r[u]] - (uint64_t)K.kmin);
+      }
+      if (K.nullable) {
+        uint64_t w[N];
+#pragma unroll
+        for (int u = 0; u < N; u++) w[u] = K.validity[r[u] >> 6];
+#pragma unroll
+        for (int u = 0; u < N; u++)
+          if (!((w[u] >> (r[u] & 63)) & 1)) dg[u] = (A)(K.radix - 1);
+      }
+#pragma unroll
+      for (int u = 0; u < N; u++) code[u] += dg[u] * (A)K.stride;
+    }
+  }
+  __device__ __forceinline__ int64_t operator()(int64_t r) const {
+    const int64_t rr[1] = {r};
+    uint64_t c[1];
+    rows(rr, c);
+    return (int64_t)c[0];
+  }
+};
+
 template <typename TK, bool HASHED = false>
 __global__ __launch_bounds__(1024) void pg_hist_kernel(const TK *__restrict__ key, int64_t n, int64_t chunk,
                                                       int64_t kmin, int shift, int np,
@@ -101,6 +153,29 @@ __global__ __launch_bounds__(1024) void pg_hist_kernel(const TK *__restrict__ ke
   for (int p = threadIdx.x; p < np; p += blockDim.x) hist[(size_t)p * gridDim.x + blockIdx.x] = h[p];
 }
 
+// ... over the group code of the plan's key columns (a sibling, so the
+// single-column kernel above compiles as it did; codes start at 0: kmin = 0)
+template <bool HASHED>
+__global__ __launch_bounds__(1024) void pg_hist_code_kernel(const PgCode key, int64_t n, int64_t chunk, int shift,
+                                                           int np, unsigned int *__restrict__ hist /* [np][grid] */) {
+  extern __shared__ unsigned int h[];
+  for (int p = threadIdx.x; p < np; p += blockDim.x) h[p] = 0;
+  __syncthreads();
+  const int64_t b = (int64_t)blockIdx.x * chunk, e = min(n, b + chunk);
+  const int64_t B = blockDim.x;
+  int64_t i = b + threadIdx.x;
+  for (; i + 3 * B < e; i += 4 * B) {  // four rows in flight per lane
+    const int64_t r[4] = {i, i + B, i + 2 * B, i + 3 * B};
+    uint64_t c[4];
+    key.rows(r, c);
+#pragma unroll
+    for (int u = 0; u < 4; u++) atomicAdd(&h[pg_part<HASHED>((int64_t)c[u], 0, shift)], 1u);
+  }
+  for (; i < e; i += B) atomicAdd(&h[pg_part<HASHED>(key(i), 0, shift)], 1u);
+  __syncthreads();
+  for (int p = threadIdx.x; p < np; p += blockDim.x) hist[(size_t)p * gridDim.x + blockIdx.x] = h[p];
+}
+
 // Rows of a workgroup's chunk in tiles of kTile: each tile is counting-sorted
 // by partition in LDS (a returning LDS add gives a row its rank in its
 // partition, a block scan the partitions' bases), staged there, and written
@@ -114,9 +189,9 @@ __global__ __launch_bounds__(1024) void pg_hist_kernel(const TK *__restrict__ ke
 // tiles in two 8-wave workgroups per CU (one stages while the other stores)
 constexpr int kScatterThreads = 512, kTile = 4096;
 
-template <typename TK, typename TV, int NV, bool PACK, int TILE>
-__global__ __launch_bounds__(TILE / 8) void pg_scatter_kernel(
-    const TK *__restrict__ key, const TV *__restrict__ v0, const TV *__restrict__ v1, int64_t n, int64_t chunk,
+template <typename TV, int NV, bool PACK, int TILE, typename KS>
+__device__ __forceinline__ void pg_scatter_body(
+    const KS &key, const TV *__restrict__ v0, const TV *__restrict__ v1, int64_t n, int64_t chunk,
     int64_t kmin, int shift, int np, const unsigned int *__restrict__ off /* [np][grid] */, uint16_t *__restrict__ ok,
     TV *__restrict__ ov0, TV *__restrict__ ov1) {
   constexpr int kTile = TILE, kScatterThreads = TILE / 8;
@@ -140,12 +215,24 @@ __global__ __launch_bounds__(TILE / 8) void pg_scatter_kernel(
   uint32_t rel[RPT];
   TV a[RPT], c[RPT];
   auto load = [&](int64_t tb) {
+    if constexpr (KS::kCode) {  // (the validity loads follow the same clamp)
+      int64_t r[RPT];
 #pragma unroll
-    for (int u = 0; u < RPT; u++) {
-      const int64_t r = min(tb + u * kScatterThreads + t, e - 1);
-      rel[u] = (uint32_t)((int64_t)key[r] - kmin);
-      if (NV >= 1) a[u] = v0[r];
-      if (NV >= 2) c[u] = v1[r];
+      for (int u = 0; u < RPT; u++) r[u] = min(tb + u * kScatterThreads + t, e - 1);
+      key.rows(r, rel);
+#pragma unroll
+      for (int u = 0; u < RPT; u++) {
+        if (NV >= 1) a[u] = v0[r[u]];
+        if (NV >= 2) c[u] = v1[r[u]];
+      }
+    } else {
+#pragma unroll
+      for (int u = 0; u < RPT; u++) {
+        const int64_t r = min(tb + u * kScatterThreads + t, e - 1);
+        rel[u] = (uint32_t)(key(r) - kmin);
+        if (NV >= 1) a[u] = v0[r];
+        if (NV >= 2) c[u] = v1[r];
+      }
     }
   };
   if (b < e) load(b);
@@ -208,6 +295,21 @@ __global__ __launch_bounds__(TILE / 8) void pg_scatter_kernel(
     __syncthreads();
     for (int p = t; p < np; p += kScatterThreads) cur[p] += cnt[p];
   }
+}
+
+template <typename TK, typename TV, int NV, bool PACK, int TILE>
+__global__ __launch_bounds__(TILE / 8) void pg_scatter_kernel(
+    const TK *__restrict__ key, const TV *__restrict__ v0, const TV *__restrict__ v1, int64_t n, int64_t chunk,
+    int64_t kmin, int shift, int np, const unsigned int *__restrict__ off /* [np][grid] */, uint16_t *__restrict__ ok,
+    TV *__restrict__ ov0, TV *__restrict__ ov1) {
+  pg_scatter_body<TV, NV, PACK, TILE>(PgCol<TK>{key}, v0, v1, n, chunk, kmin, shift, np, off, ok, ov0, ov1);
+}
+template <typename TV, int NV, bool PACK, int TILE>
+__global__ __launch_bounds__(TILE / 8) void pg_scatter_code_kernel(
+    const PgCode key, const TV *__restrict__ v0, const TV *__restrict__ v1, int64_t n, int64_t chunk, int shift,
+    int np, const unsigned int *__restrict__ off, uint16_t *__restrict__ ok, TV *__restrict__ ov0,
+    TV *__restrict__ ov1) {
+  pg_scatter_body<TV, NV, PACK, TILE>(key, v0, v1, n, chunk, (int64_t)0, shift, np, off, ok, ov0, ov1);
 }
 
 // the reduce passes' piece: at most 2^20 rows, and the piece count a multiple
@@ -370,9 +472,9 @@ constexpr int kHashSlots = 4096;   // LDS table of a piece
 constexpr int kHashGlobal = 8192;  // global table per partition
 constexpr uint64_t kMsb = 0x8000000000000000ull;
 
-template <typename TK, typename TV, int NV>
-__global__ __launch_bounds__(kHThreads) void pg_hscatter_kernel(
-    const TK *__restrict__ key, const TV *__restrict__ v0, int64_t n, int64_t chunk, int pbits, int np,
+template <typename TV, int NV, typename KS>
+__device__ __forceinline__ void pg_hscatter_body(
+    const KS &key, const TV *__restrict__ v0, int64_t n, int64_t chunk, int pbits, int np,
     const unsigned int *__restrict__ off, int64_t *__restrict__ rec /* [n][NV + 1] */) {
   constexpr int kTile = kHTile, kScatterThreads = kHThreads;
   constexpr int RPT = kTile / kScatterThreads, RS = NV + 1;
@@ -392,11 +494,24 @@ __global__ __launch_bounds__(kHThreads) void pg_hscatter_kernel(
   // and stores into the pad slot after the records.
   int64_t kk[RPT], vv[RPT];
   auto load = [&](int64_t tb) {
+    if constexpr (KS::kCode) {
+      int64_t r[RPT];
 #pragma unroll
-    for (int u = 0; u < RPT; u++) {
-      const int64_t r = min(tb + u * kScatterThreads + t, e - 1);
-      kk[u] = (int64_t)key[r];
-      if (NV >= 1) vv[u] = (int64_t)v0[r];
+      for (int u = 0; u < RPT; u++) r[u] = min(tb + u * kScatterThreads + t, e - 1);
+      uint64_t code[RPT];
+      key.rows(r, code);
+#pragma unroll
+      for (int u = 0; u < RPT; u++) {
+        kk[u] = (int64_t)code[u];
+        if (NV >= 1) vv[u] = (int64_t)v0[r[u]];
+      }
+    } else {
+#pragma unroll
+      for (int u = 0; u < RPT; u++) {
+        const int64_t r = min(tb + u * kScatterThreads + t, e - 1);
+        kk[u] = key(r);
+        if (NV >= 1) vv[u] = (int64_t)v0[r];
+      }
     }
   };
   if (b < e) load(b);
@@ -457,6 +572,20 @@ __global__ __launch_bounds__(kHThreads) void pg_hscatter_kernel(
     __syncthreads();
     for (int p = t; p < np; p += kScatterThreads) cur[p] += cnt[p];
   }
+}
+
+template <typename TK, typename TV, int NV>
+__global__ __launch_bounds__(kHThreads) void pg_hscatter_kernel(
+    const TK *__restrict__ key, const TV *__restrict__ v0, int64_t n, int64_t chunk, int pbits, int np,
+    const unsigned int *__restrict__ off, int64_t *__restrict__ rec /* [n][NV + 1] */) {
+  pg_hscatter_body<TV, NV>(PgCol<TK>{key}, v0, n, chunk, pbits, np, off, rec);
+}
+// (codes are >= 0: code ^ 2^63 is never 0, the INT64_MIN slot stays unused)
+template <typename TV, int NV>
+__global__ __launch_bounds__(kHThreads) void pg_hscatter_code_kernel(
+    const PgCode key, const TV *__restrict__ v0, int64_t n, int64_t chunk, int pbits, int np,
+    const unsigned int *__restrict__ off, int64_t *__restrict__ rec) {
+  pg_hscatter_body<TV, NV>(key, v0, n, chunk, pbits, np, off, rec);
 }
 
 template <int NV, bool MM, bool PC>
@@ -596,7 +725,7 @@ __global__ __launch_bounds__(1024) void pg_hreduce_kernel(const int64_t *__restr
 
 bool PartGroupHashed(const PartGroupDesc &d, unsigned long long *gkeys, int *overflow, hipStream_t s) {
   if (d.n <= 0 || d.n >= ((int64_t)1 << 32) || d.nv < 0 || d.nv > 1) return false;
-  if (d.kphys != P_I32 && d.kphys != P_I64) return false;
+  if (!d.code && d.kphys != P_I32 && d.kphys != P_I64) return false;
   if (d.nv > 0 && d.vphys != P_I32 && d.vphys != P_I64) return false;
   const int pbits = kHashParts, np = 1 << pbits;
   int64_t piece = BalancedPiece(d.n);
@@ -611,7 +740,12 @@ bool PartGroupHashed(const PartGroupDesc &d, unsigned long long *gkeys, int *ove
   unsigned int *start = (unsigned int *)d.scratch_start;
   int64_t *rec = (int64_t *)d.scratch_rows;
   const size_t hl = (size_t)np * 4;
-  if (d.kphys == P_I64)
+  PgCode code;
+  if (d.code) code.plan = *d.code;
+  if (d.code)
+    hipLaunchKernelGGL((pg_hist_code_kernel<true>), dim3(grid), dim3(kHThreads), hl, s, code, d.n, chunk, pbits, np,
+                       hist);
+  else if (d.kphys == P_I64)
     hipLaunchKernelGGL((pg_hist_kernel<int64_t, true>), dim3(grid), dim3(kHThreads), hl, s,
                        (const int64_t *)d.key, d.n, chunk, (int64_t)0, pbits, np, hist);
   else
@@ -636,7 +770,19 @@ bool PartGroupHashed(const PartGroupDesc &d, unsigned long long *gkeys, int *ove
   if (d.nv == 0) PHS(TK, int64_t, 0)                                                                                \
   else if (d.vphys == P_I64) PHS(TK, int64_t, 1)                                                                    \
   else PHS(TK, int32_t, 1)
-  if (d.kphys == P_I64) { PHSV(int64_t) } else { PHSV(int32_t) }
+#define PHSC(TV, NV)                                                                                                \
+  {                                                                                                                 \
+    (void)hipFuncSetAttribute((const void *)pg_hscatter_code_kernel<TV, NV>,                                        \
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)sl);                                 \
+    hipLaunchKernelGGL((pg_hscatter_code_kernel<TV, NV>), dim3(grid), dim3(kHThreads), sl, s, code,                 \
+                       (const TV *)d.v0, d.n, chunk, pbits, np, off, rec);                                          \
+  }
+  if (d.code) {
+    if (d.nv == 0) PHSC(int64_t, 0)
+    else if (d.vphys == P_I64) PHSC(int64_t, 1)
+    else PHSC(int32_t, 1)
+  } else if (d.kphys == P_I64) { PHSV(int64_t) } else { PHSV(int32_t) }
+#undef PHSC
 #undef PHSV
 #undef PHS
   const int64_t total = (int64_t)np * kHashGlobal + 1;
@@ -691,7 +837,8 @@ int64_t PartGroupMaxRange(int nv, bool mm) { return (int64_t)kPartGroupMaxParts 
 
 bool PartGroup(const PartGroupDesc &d, hipStream_t s) {
   if (d.range <= 0 || d.range > PartGroupMaxRange(d.nv, d.mm) || d.n <= 0 || d.n >= ((int64_t)1 << 32)) return false;
-  if (d.nv < 0 || d.nv > 2 || (d.kphys != P_I32 && d.kphys != P_I64)) return false;
+  if (d.nv < 0 || d.nv > 2 || (!d.code && d.kphys != P_I32 && d.kphys != P_I64)) return false;
+  if (d.code && (d.kmin != 0 || d.range != d.code->total)) return false;
   if (d.nv > 0 && d.vphys != P_I32 && d.vphys != P_I64) return false;
   const int shift = PartGroupShift(d.nv, d.mm);
   const int np = (int)((d.range + (1 << shift) - 1) >> shift);
@@ -723,7 +870,12 @@ bool PartGroup(const PartGroupDesc &d, hipStream_t s) {
   void *rv0 = (char *)d.scratch_rows + PadUp((size_t)d.n * 2);
   void *rv1 = (char *)rv0 + PadUp((size_t)d.n * vb);
   const size_t hl = (size_t)np * 4;
-  if (d.kphys == P_I64)
+  PgCode code;
+  if (d.code) code.plan = *d.code;
+  if (d.code)
+    hipLaunchKernelGGL(pg_hist_code_kernel<false>, dim3(grid), dim3(sthreads), hl, s, code, d.n, chunk, shift, np,
+                       hist);
+  else if (d.kphys == P_I64)
     hipLaunchKernelGGL(pg_hist_kernel<int64_t>, dim3(grid), dim3(sthreads), hl, s, (const int64_t *)d.key,
                        d.n, chunk, d.kmin, shift, np, hist);
   else
@@ -758,7 +910,29 @@ bool PartGroup(const PartGroupDesc &d, hipStream_t s) {
     else if (d.nv == 1) PGS(TK, int32_t, 1, false)                                                                  \
     else PGS(TK, int32_t, 2, false)                                                                                 \
   }
-  if (d.kphys == P_I64) { PGSV(int64_t) } else { PGSV(int32_t) }
+// the same launch over the group code
+#define PGC1(TV, NV, PK, T)                                                                                         \
+  {                                                                                                                 \
+    (void)hipFuncSetAttribute((const void *)pg_scatter_code_kernel<TV, NV, PK, T>,                                  \
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)sl);                                 \
+    hipLaunchKernelGGL((pg_scatter_code_kernel<TV, NV, PK, T>), dim3(grid), dim3(T / 8), sl, s, code,               \
+                       (const TV *)d.v0, (const TV *)d.v1, d.n, chunk, shift, np, off, rk, (TV *)rv0, (TV *)rv1);   \
+  }
+#define PGC(TV, NV, PK)                                                                                             \
+  if (tile == 8192) PGC1(TV, NV, PK, 8192) else PGC1(TV, NV, PK, 4096)
+  if (d.code) {
+    if (d.vphys == P_I64) {
+      if (d.nv == 0) PGC(int64_t, 0, false)
+      else if (d.nv == 1) { if (pack) PGC(int64_t, 1, true) else PGC(int64_t, 1, false) }
+      else PGC(int64_t, 2, false)
+    } else {
+      if (d.nv == 0) PGC(int32_t, 0, false)
+      else if (d.nv == 1) PGC(int32_t, 1, false)
+      else PGC(int32_t, 2, false)
+    }
+  } else if (d.kphys == P_I64) { PGSV(int64_t) } else { PGSV(int32_t) }
+#undef PGC
+#undef PGC1
 #undef PGSV
 #undef PGS
 #undef PGS1

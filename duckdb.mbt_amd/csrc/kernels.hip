@@ -2586,7 +2586,8 @@ __device__ __forceinline__ void emit_agg_body(const EmitDesc &D, Acc *part, int6
       const auto &K = D.kc[q];
       bool kv = in;
       if (in) {
-        const int64_t dg = (sl / K.stride) % K.radix;
+        const int64_t code = D.code_msb ? (int64_t)(D.code_msb[sl] ^ 0x8000000000000000ull) : sl;
+        const int64_t dg = (code / K.stride) % K.radix;
         kv = !(K.nullable && dg == K.radix - 1);
         const int64_t k = kv ? K.kmin + dg : 0;
         store_phys(K.out, K.phys, i, k, k >> 63);
