@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "group_code.h"
+#include "scan_codes.h"
 #include "vm.h"
 
 namespace mbx {
@@ -82,6 +83,16 @@ int FilterMultiPartials(const FilterMultiDesc &d, int64_t nrows, AggPartial *par
 int FilterAggStates(const void *pcol, int pphys, int64_t lo, int64_t hi, bool has_pred, const void *acol, int aphys,
                     int64_t nrows, AggState *st, unsigned long long *cstar, int grid_blocks, hipStream_t s,
                     bool need_minmax = true, uint64_t sum_maxabs = ~0ull, AggPartial *partials = nullptr);
+// The same over a column's code image (scan_codes.h): `width`-byte codes of
+// value - base, predicate clo <= code <= clo + cspan (PlanScanCodeRange).
+// sum = false: COUNT(*) only; else COUNT / SUM (and MIN / MAX) of the passing
+// values.  Always writes per-workgroup partials and returns their count (> 0).
+int FilterAggCodes(const void *codes, int width, int64_t base, uint32_t clo, uint32_t cspan, bool packed, bool sum,
+                   bool need_minmax, int64_t nrows, AggPartial *partials, hipStream_t s);
+// codes[i] = (uint<width>)(values[i] - base) for rows [begin, end) of a P_I32 /
+// P_I64 column (both buffers 256-B aligned at row 0)
+void ScanEncode(const void *values, int phys, void *codes, int width, int64_t base, int64_t begin, int64_t end,
+                hipStream_t s);
 
 // --- fused GROUP BY on a small-range integer key (config C3) -------------
 // key in [kmin, kmin + nk) (the NULL group in slot nk - 1 when the key has

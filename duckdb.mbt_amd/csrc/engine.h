@@ -41,6 +41,17 @@ struct DevColumn {
   bool stats_valid = false;
   i128 imin = 0, imax = 0;
   int64_t null_count = 0;
+  // code image (scan_codes.h) of a narrow-range P_I32 / P_I64 column without
+  // NULLs: codes[i] = (uint<code_width * 8>)(value[i] - code_base) for rows
+  // [0, code_rows), in its own 256-B-aligned buffer.  Built at ingest once the
+  // zone map is folded, extended by appends that fit the base and width,
+  // rebuilt when the base moves, freed when the range outgrows the width.  The
+  // fused filter-aggregate streams it in place of the values when code_rows
+  // covers the table; `data` stays the column's truth for every other reader.
+  void *codes = nullptr;
+  std::shared_ptr<void> codes_owner;
+  int code_width = 0;  // 0: no image
+  int64_t code_base = 0, code_rows = 0, code_cap = 0;
 };
 
 struct Table {
@@ -158,6 +169,12 @@ struct Options {
   // "mbx_shard_rows": appends fill part i of a sharded table up to this many
   // rows before moving on to part i + 1 (0: appends go to the last part)
   int64_t shard_rows = 0;
+  // "mbx_scan_codes": keep a 1- or 2-byte code image of narrow-range integer
+  // columns and scan it in the fused filter-aggregate (false: none is built)
+  bool scan_codes = true;
+  // "mbx_scan_codes_min_rows": tables below this many rows get no image (their
+  // scan is launch-bound: 2^20 rows of 8 bytes stream in ~1 us)
+  int64_t scan_codes_min_rows = (int64_t)1 << 20;
   // "mbx_force_peer" (tests): shards on the same device still exchange row
   // results by peer DMA (hipMemcpyPeerAsync), as distinct devices do
   bool force_peer = false;

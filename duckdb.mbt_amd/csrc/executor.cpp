@@ -166,6 +166,7 @@ struct Engine {
     long long *h;  // pinned: min, max, non-null count
     int64_t n;
     bool first_rows;
+    int64_t rows;  // the table's row count after this append
   };
   std::vector<PendingStat> pending_stats;
   std::vector<long long *> stat_slots;  // free pinned 3-value slots
@@ -176,6 +177,9 @@ struct Engine {
   // gave up because a workgroup was never scheduled (the two-pass form reran
   // the query), launches that failed to start
   int64_t sr_launches = 0, sr_aborts = 0, sr_launch_failures = 0;
+  // the connection's mbx_scan_codes / mbx_scan_codes_min_rows (set by Eng)
+  bool scan_codes = true;
+  int64_t scan_codes_min_rows = 0;
   bool profile = false;
   std::vector<ProfEvent> events;
   // kernels timed on shard engines during this query (gpu_devices)
@@ -285,8 +289,11 @@ static void FoldStats(DevColumn &c, int64_t n, int64_t nvalid, i128 mn, i128 mx,
   }
 }
 
+static void UpdateScanCodes(Engine &e, DevColumn &c, int64_t nrows);
+
 // folds the zone-map statistics of in-flight appends into their columns
-// (after the stream has drained: their DMAs and reductions are done)
+// (after the stream has drained: their DMAs and reductions are done), then
+// brings the columns' code images up to the appended rows
 static void SettlePending(Engine &e) {
   if (e.pending_stats.empty() && !e.inflight_h2d) return;
   HIPCHK(hipStreamSynchronize(e.stream));
@@ -296,7 +303,14 @@ static void SettlePending(Engine &e) {
     FoldStats(*ps.col, ps.n, h[2], h[0], h[1], ps.first_rows);
     e.stat_slots.push_back(ps.h);
   }
+  std::vector<std::pair<DevColumn *, int64_t>> cols;  // each column once, at its last row count
+  for (auto &ps : e.pending_stats) {
+    auto it = std::find_if(cols.begin(), cols.end(), [&](const std::pair<DevColumn *, int64_t> &x) { return x.first == ps.col; });
+    if (it == cols.end()) cols.push_back({ps.col, ps.rows});
+    else it->second = std::max(it->second, ps.rows);
+  }
   e.pending_stats.clear();
+  for (auto &cr : cols) UpdateScanCodes(e, *cr.first, cr.second);
 }
 
 static Engine &Eng(Connection &c) {
@@ -305,6 +319,8 @@ static Engine &Eng(Connection &c) {
     ThrowError("IO", "this statement reads table rows and needs the MI355X device, but no GPU is available");
   hipSetDevice(e.device);
   dev::SetTempAllocator(&TempAllocCb, &TempFreeCb, e.pool.get());
+  e.scan_codes = c.opts.scan_codes;
+  e.scan_codes_min_rows = c.opts.scan_codes_min_rows;
   SettlePending(e);  // a statement never sees a column before its appended stats
   return e;
 }
@@ -390,7 +406,7 @@ struct DRel {
 
 static DCol ColFromTable(const DevColumn &c) {
   DCol d;
-  for (const auto *o : {&c.data_owner, &c.validity_owner, &c.offsets_owner, &c.chars_owner})
+  for (const auto *o : {&c.data_owner, &c.validity_owner, &c.offsets_owner, &c.chars_owner, &c.codes_owner})
     if (*o) d.pins.push_back(*o);
   d.type = c.type;
   d.phys = c.phys;
@@ -2435,10 +2451,28 @@ static DRel Aggregate(Engine &e, const DRel &src, const BoundSelect &s) {
         double bytes = 0;
         if (P) bytes += (double)src.n * PhysSize(P->phys);
         if (A && A != P) bytes += (double)src.n * PhysSize(A->phys);
-        if (P) {
+        // The predicate column's code image stands in for its values when it
+        // covers exactly these rows and the aggregates, if any, read the same
+        // column; a slice, an intermediate or a second column reads the values.
+        const DevColumn *tc = P ? P->table_col : nullptr;
+        const bool by_codes = e.scan_codes && tc && tc->codes && P->data == tc->data && src.n == tc->code_rows &&
+                              (!A || A == P) && src.n < ((int64_t)1 << 40);
+        bool need_mm = false;
+        for (auto &a : s.aggs) need_mm |= a.kind == A_MIN || a.kind == A_MAX;
+        if (by_codes) {
+          const ScanCodeRange cr = PlanScanCodeRange(tc->code_width, (i128)tc->code_base, tc->imax, (int64_t)lo, (int64_t)hi);
+          if (cr.empty) {
+            // the zone map rules every row out: no scan (the entry keeps the
+            // profile at one filter_agg per statement, with nothing read)
+            ProfScope ps(e, "filter_agg", 0, src.n);
+            dev::InitAggStatesCounts(st, 1, cstar, 1, e.stream);
+          } else {
+            ProfScope ps(e, "filter_agg", (double)src.n * tc->code_width, src.n);
+            npartials = dev::FilterAggCodes(tc->codes, tc->code_width, tc->code_base, cr.clo, cr.cspan, cr.packed,
+                                            A != nullptr, need_mm, src.n, e.d_partials, e.stream);
+          }
+        } else if (P) {
           ProfScope ps(e, "filter_agg", bytes, src.n);
-          bool need_mm = false;
-          for (auto &a : s.aggs) need_mm |= a.kind == A_MIN || a.kind == A_MAX;
           // zone-map bound on |value| of the aggregated column (lets the kernel
           // keep int64 per-lane partial sums; ~0 = unknown)
           uint64_t maxabs = ~0ull;
@@ -3739,6 +3773,47 @@ static void Grow(Engine &e, DevColumn &c, int64_t nrows_old, int64_t need) {
   c.capacity = cap;
 }
 
+// Brings c's code image (scan_codes.h) up to nrows rows, once the zone map of
+// every row is folded: the appended tail when the map still fits the image's
+// base and width, all rows when the base or the width changed, and no image
+// when the column does not qualify.  A column is never left partly coded
+// beyond this call: code_rows is nrows or the image is gone.
+static void UpdateScanCodes(Engine &e, DevColumn &c, int64_t nrows) {
+  int w = 0;
+  if (e.scan_codes && nrows > 0 && nrows >= e.scan_codes_min_rows && c.stats_valid && !c.validity &&
+      c.null_count == 0 && c.data)
+    w = ScanCodeWidth(c.phys, c.imin, c.imax);
+  if (!w) {
+    c.codes = nullptr;
+    c.codes_owner.reset();
+    c.code_width = 0;
+    c.code_base = c.code_rows = c.code_cap = 0;
+    return;
+  }
+  const bool extend = c.codes && c.code_width == w && c.code_base == (int64_t)c.imin && c.code_rows <= nrows;
+  const int64_t begin = extend ? c.code_rows : 0;
+  if (begin == nrows) return;
+  if (!extend || c.code_cap < nrows) {
+    const int64_t cap = std::max<int64_t>(nrows, c.capacity);
+    void *nc = nullptr;
+    HIPCHK(hipMalloc(&nc, (size_t)cap * w));
+    if (begin > 0) {
+      HIPCHK(hipMemcpyAsync(nc, c.codes, (size_t)begin * w, hipMemcpyDeviceToDevice, e.stream));
+      HIPCHK(hipStreamSynchronize(e.stream));  // before the old image goes
+    }
+    c.codes_owner = DevOwned(e, nc);
+    c.codes = nc;
+    c.code_cap = cap;
+    c.code_width = w;
+    c.code_base = (int64_t)c.imin;
+  }
+  {
+    ProfScope ps(e, "scan_encode", (double)(nrows - begin) * (PhysSize(c.phys) + w), nrows - begin);
+    dev::ScanEncode(c.data, c.phys, c.codes, w, c.code_base, begin, nrows, e.stream);
+  }
+  c.code_rows = nrows;
+}
+
 static void EnsureValidity(Engine &e, DevColumn &c, int64_t nrows_old) {
   if (c.validity) return;
   int64_t cap = std::max<int64_t>(c.capacity, 1);
@@ -3786,7 +3861,7 @@ static void UpdateStats(Engine &e, DevColumn &c, int64_t off, int64_t n, bool fi
       HIPCHK(hipHostMalloc((void **)&slot, 3 * sizeof(long long), hipHostMallocDefault));
     }
     HIPCHK(hipMemcpyAsync(slot, o3, 3 * sizeof(long long), hipMemcpyDeviceToHost, e.stream));
-    e.pending_stats.push_back({&c, slot, n, first_rows});
+    e.pending_stats.push_back({&c, slot, n, first_rows, off + n});
     return;
   }
   long long h[3];
@@ -3888,6 +3963,7 @@ static void AppendDRel(Engine &e, Table &t, const DRel &r, const std::vector<int
   }
   HIPCHK(hipStreamSynchronize(e.stream));
   t.nrows = old + n;
+  for (auto &c : t.cols) UpdateScanCodes(e, c, t.nrows);
 }
 
 static void AppendCast(Engine &e, Table &t, DRel r, const std::vector<int> &col_map);
@@ -5563,6 +5639,7 @@ void AppendRawColumns(Connection &c, Table &t, const std::vector<const void *> &
     return;
   }
   HIPCHK(hipStreamSynchronize(e.stream));
+  for (auto &col : t.cols) UpdateScanCodes(e, col, t.nrows);
   CheckError(e);
 }
 

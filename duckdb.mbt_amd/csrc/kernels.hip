@@ -15,6 +15,7 @@
 #include <limits>
 #include <stdexcept>
 #include <stdint.h>
+#include <type_traits>
 
 #include "device.h"
 #include "types.h"
@@ -681,6 +682,154 @@ __global__ __launch_bounds__(256) void filter_agg_lds_kernel(const T *__restrict
   }
 }
 
+// The same ring over a column's code image (scan_codes.h): W-byte codes
+// (value - base), a 1-KiB piece is 1024 / W rows, 16 / W codes per lane.  The
+// predicate is clo <= code <= clo + cspan.  MODE 2 counts; MODE 0 also sums the
+// passing codes (and, MM, takes their min / max).  PACKED (every code of the
+// column below 128 / 32768): the compare runs on whole 32-bit words
+// (ScanPackedMask), the count is a popcount and the sum a masked v_sad_u8.
+// Per piece a lane adds at most 16 x 65535 to 32-bit piece totals, folded into
+// 64-bit lane totals; the value sum is codes + count x base in int128, once
+// per lane, so the partial records are exactly those of the 8-byte kernel.
+template <int W, int MODE, int DEPTH, bool MM, bool PACKED>
+__global__ __launch_bounds__(256) void filter_agg_codes_kernel(const unsigned char *__restrict__ codes, int64_t n,
+                                                               uint32_t clo, uint32_t cspan, int64_t base,
+                                                               AggPartial *partials) {
+  constexpr int64_t RP = 1024 / W;
+  constexpr int CPW = 4 / W;  // codes per 32-bit word
+  __shared__ __attribute__((aligned(16))) v4i32 ring[4 * DEPTH * 64];
+  static_assert(sizeof(v4i32) * 4 * DEPTH * 64 >= 4 * sizeof(Acc), "the block reduction reuses the ring");
+  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int64_t npieces = n / RP;
+  const int64_t nw = (int64_t)gridDim.x * 4;
+  int64_t pc = (int64_t)blockIdx.x * 4 + w;
+  v4i32 *slot0 = ring + w * DEPTH * 64;
+  const v4i32 *P = (const v4i32 *)codes;
+  const uint32_t H = ScanPackedTop(W), PA = ScanPackedA(W, PACKED ? clo : 0), PB = ScanPackedB(W, PACKED ? clo + cspan : 0);
+  uint64_t cnt = 0, sum = 0;
+  int32_t mn = INT32_MAX, mx = -1;  // codes are below 2^16
+  auto one = [&](uint32_t c, uint32_t &pcnt, uint32_t &psum) {
+    const bool ok = c - clo <= cspan;
+    pcnt += ok;
+    if (MODE == 0) psum += ok ? c : 0u;
+    if (MM) {
+      mn = min(mn, ok ? (int32_t)c : INT32_MAX);
+      mx = max(mx, ok ? (int32_t)c : -1);
+    }
+  };
+  auto word = [&](uint32_t x, uint32_t &pcnt, uint32_t &psum) {
+    if (PACKED && !MM) {
+      const uint32_t m = ScanPackedMask(x, PA, PB, H);
+      pcnt += __builtin_popcount(m);
+      if (MODE == 0) {
+        if (W == 1) {
+          psum = __builtin_amdgcn_sad_u8(x & ((m >> 7) * 0xFFu), 0u, psum);
+        } else {
+          const uint32_t t = x & ((m >> 15) * 0xFFFFu);
+          psum += (t & 0xFFFFu) + (t >> 16);
+        }
+      }
+    } else {
+#pragma unroll
+      for (int e = 0; e < CPW; e++) one(W == 1 ? (x >> (8 * e)) & 0xFFu : (x >> (16 * e)) & 0xFFFFu, pcnt, psum);
+    }
+  };
+#pragma unroll
+  for (int d = 0; d < DEPTH; d++) {
+    int64_t q = pc + d * nw;
+    q = q < npieces ? q : 0;  // keep the per-slot load count uniform (dummy piece 0)
+    if (npieces > 0) __builtin_amdgcn_global_load_lds((const void *)(P + q * 64 + lane), (void *)(slot0 + d * 64), 16, 0, 2);
+  }
+  int k = 0;
+  for (; pc < npieces; pc += nw) {
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(DEPTH - 1) : "memory");
+    v4i32 x = slot0[k * 64 + lane];
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    int64_t q = pc + DEPTH * nw;
+    q = q < npieces ? q : pc;  // past the end: re-read the piece just consumed
+    __builtin_amdgcn_global_load_lds((const void *)(P + q * 64 + lane), (void *)(slot0 + k * 64), 16, 0, 2);
+    uint32_t pcnt = 0, psum = 0;
+    word((uint32_t)x.x, pcnt, psum);
+    word((uint32_t)x.y, pcnt, psum);
+    word((uint32_t)x.z, pcnt, psum);
+    word((uint32_t)x.w, pcnt, psum);
+    cnt += pcnt;
+    sum += psum;
+    k = k + 1 == DEPTH ? 0 : k + 1;
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  if (blockIdx.x == 0 && w == 0) {
+    uint32_t pcnt = 0, psum = 0;
+    for (int64_t i = npieces * RP + lane; i < n; i += 64)
+      one(W == 1 ? (uint32_t)codes[i] : (uint32_t)((const uint16_t *)codes)[i], pcnt, psum);
+    cnt += pcnt;
+    sum += psum;
+  }
+  Acc A;
+  A.cnt = cnt;
+  {
+    const __int128 s = (__int128)(unsigned __int128)sum + (__int128)(unsigned __int128)cnt * (__int128)base;
+    A.slo = (uint64_t)s;
+    A.shi = (int64_t)(s >> 64);
+  }
+  A.mn = MM && mx >= 0 ? (int64_t)((uint64_t)base + (uint64_t)mn) : INT64_MAX;
+  A.mx = MM && mx >= 0 ? (int64_t)((uint64_t)base + (uint64_t)mx) : INT64_MIN;
+  acc_wave_reduce(A);
+  __syncthreads();
+  Acc *part = (Acc *)ring;
+  if (lane == 0) part[w] = A;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    Acc T0 = part[0];
+    for (int i = 1; i < 4; i++) acc_merge(T0, part[i]);
+    partials[blockIdx.x] = AggPartial{T0.cnt, T0.slo, T0.shi, T0.mn, T0.mx};
+  }
+}
+
+// Builds the code image of rows [begin, end): code[i] = (C)(value[i] - base).
+// Whole 16-byte groups of values from the first row that is a multiple of 16
+// (so the packed stores stay aligned), the rows before and after one by one.
+template <typename T, typename C>
+__global__ __launch_bounds__(256) void scan_encode_kernel(const T *__restrict__ v, C *__restrict__ code, int64_t begin,
+                                                          int64_t end, uint64_t base) {
+  constexpr int R = 16 / (int)sizeof(T);
+  typedef typename std::conditional<sizeof(C) * R == 2, uint16_t, uint32_t>::type Out;
+  static_assert(sizeof(C) * R == sizeof(Out), "one packed store per 16-byte load");
+  int64_t a = (begin + 15) & ~(int64_t)15;
+  if (a > end) a = end;
+  const int64_t nvec = (end - a) / R;
+  const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (int64_t)gridDim.x * blockDim.x;
+  const v4i32 *src = (const v4i32 *)(v + a);
+  Out *dst = (Out *)(code + a);
+  auto pack = [&](v4i32 x) -> Out {
+    if (sizeof(T) == 8) {
+      const uint64_t c0 = ((uint64_t)(uint32_t)x.x | ((uint64_t)(uint32_t)x.y << 32)) - base;
+      const uint64_t c1 = ((uint64_t)(uint32_t)x.z | ((uint64_t)(uint32_t)x.w << 32)) - base;
+      return (Out)((uint32_t)(C)c0 | ((uint32_t)(C)c1 << (8 * sizeof(C))));
+    }
+    uint32_t o = 0;
+    const int xs[4] = {x.x, x.y, x.z, x.w};
+#pragma unroll
+    for (int e = 0; e < 4; e++) o |= (uint32_t)(C)((uint64_t)(int64_t)xs[e] - base) << (8 * sizeof(C) * e);
+    return (Out)o;
+  };
+  int64_t i = tid;
+  for (; i + 3 * stride < nvec; i += 4 * stride) {
+    const v4i32 x0 = __builtin_nontemporal_load(src + i), x1 = __builtin_nontemporal_load(src + i + stride);
+    const v4i32 x2 = __builtin_nontemporal_load(src + i + 2 * stride), x3 = __builtin_nontemporal_load(src + i + 3 * stride);
+    dst[i] = pack(x0);
+    dst[i + stride] = pack(x1);
+    dst[i + 2 * stride] = pack(x2);
+    dst[i + 3 * stride] = pack(x3);
+  }
+  for (; i < nvec; i += stride) dst[i] = pack(src[i]);
+  const int64_t nhead = a - begin, t0 = a + nvec * R, ntail = end - t0;
+  for (int64_t j = tid; j < nhead + ntail; j += stride) {
+    const int64_t row = j < nhead ? begin + j : t0 + (j - nhead);
+    code[row] = (C)((uint64_t)(int64_t)v[row] - base);
+  }
+}
+
 // Multi-column version of the LDS-DMA filter-aggregate.  A wave step covers
 // 256 consecutive rows; each column's slice (1 KiB for int32, 2 KiB for
 // int64) lands in the wave's ring slot through global_load_lds; each lane
@@ -1310,6 +1459,45 @@ int FilterAggStates(const void *pcol, int pphys, int64_t lo, int64_t hi, bool ha
   }
   g_fa_partials = nullptr;
   return use_partials ? grid : 0;
+}
+
+int FilterAggCodes(const void *codes, int width, int64_t base, uint32_t clo, uint32_t cspan, bool packed, bool sum,
+                   bool need_minmax, int64_t nrows, AggPartial *partials, hipStream_t s) {
+  int grid = NumCUs();
+  if (grid > kMaxAggPartials) grid = kMaxAggPartials;
+  const int64_t pieces = nrows / (1024 / width) + 1;
+  if ((int64_t)grid * 4 > pieces) grid = (int)((pieces + 3) / 4);
+#define FAC(W, MODE, MM, PK)                                                                                 \
+  hipLaunchKernelGGL((filter_agg_codes_kernel<W, MODE, 6, MM, PK>), dim3(grid), dim3(256), 0, s,              \
+                     (const unsigned char *)codes, nrows, clo, cspan, base, partials)
+#define FAC_W(W)                                                         \
+  if (!sum) { if (packed) FAC(W, 2, false, true); else FAC(W, 2, false, false); } \
+  else if (need_minmax) FAC(W, 0, true, false);                          \
+  else if (packed) FAC(W, 0, false, true);                               \
+  else FAC(W, 0, false, false)
+  if (width == 1) { FAC_W(1); }
+  else { FAC_W(2); }
+#undef FAC_W
+#undef FAC
+  CHECK_LAUNCH();
+  return grid;
+}
+
+void ScanEncode(const void *values, int phys, void *codes, int width, int64_t base, int64_t begin, int64_t end,
+                hipStream_t s) {
+  if (end <= begin) return;
+  const int64_t units = (end - begin) / 16 + 1;  // a thread takes 4 16-byte groups per trip
+  const int grid = (int)std::min<int64_t>((units + 255) / 256, (int64_t)NumCUs() * 8);
+  if (phys == P_I64 && width == 1)
+    hipLaunchKernelGGL((scan_encode_kernel<int64_t, uint8_t>), dim3(grid), dim3(256), 0, s, (const int64_t *)values,
+                       (uint8_t *)codes, begin, end, (uint64_t)base);
+  else if (phys == P_I64)
+    hipLaunchKernelGGL((scan_encode_kernel<int64_t, uint16_t>), dim3(grid), dim3(256), 0, s, (const int64_t *)values,
+                       (uint16_t *)codes, begin, end, (uint64_t)base);
+  else
+    hipLaunchKernelGGL((scan_encode_kernel<int32_t, uint8_t>), dim3(grid), dim3(256), 0, s, (const int32_t *)values,
+                       (uint8_t *)codes, begin, end, (uint64_t)base);
+  CHECK_LAUNCH();
 }
 
 __global__ __launch_bounds__(256) void copy_kernel(const float4 *__restrict__ in, float4 *__restrict__ out, int64_t n) {
