@@ -198,7 +198,7 @@ namespace rc {
 struct Comms;  // RCCL communicators over the shard devices (rccl_combine.h)
 struct Init;   // their open, in flight on a helper thread
 }
-struct ShardWorkers;  // persistent per-shard host threads (executor.cpp)
+struct ShardWorkers;  // persistent per-shard host threads (sharded.cpp)
 
 // Counters of the multi-device path (duckdb_mbx_shard_stats).
 struct ShardStats {
@@ -290,7 +290,8 @@ ResultPtr RunStatement(Connection &c, const std::string &sql, const std::vector<
 ResultPtr RunParsed(Connection &c, const Statement &st, const std::vector<Value> &params);
 std::string Explain(Connection &c, const std::string &sql);
 
-// Executor entry points (executor.cpp).
+// Executor entry points (executor.cpp; tables and appends in ingest.cpp, the
+// multi-device plans and the RCCL JSON in sharded.cpp).
 std::shared_ptr<Engine> CreateEngine(int device, bool allow_no_gpu);
 ResultPtr ExecuteSelect(Connection &c, const BoundSelect &s);
 DeviceResultPtr ExecuteSelectDevice(Connection &c, const BoundSelect &s, StreamSource *meta);

@@ -1,0 +1,335 @@
+// exec.h — what the executor's translation units share (executor.cpp,
+// aggregate.cpp, ingest.cpp, sharded.cpp): the engine state, device buffers
+// and relations, and the functions that cross between the units.  Internal to
+// those four files: the engine and the C-ABI shim see engine.h only.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstring>
+#include <map>
+#include <memory>
+#include <mutex>
+#include <string>
+#include <utility>
+#include <vector>
+
+#include "device.h"
+#include "engine.h"
+
+namespace mbx {
+#define HIPCHK(x)                                                                            \
+  do {                                                                                       \
+    hipError_t e_ = (x);                                                                     \
+    if (e_ != hipSuccess) ThrowError("IO", std::string("HIP error: ") + hipGetErrorString(e_) + " at " #x); \
+  } while (0)
+
+// ---------------------------------------------------------------------------
+// engine state
+// ---------------------------------------------------------------------------
+struct ProfEvent {
+  std::string name;
+  hipEvent_t a, b;
+  double bytes;
+  int64_t rows;
+};
+
+// Caching device allocator for every intermediate buffer of a connection
+// (hipMalloc underneath; the stream-ordered hipMallocAsync pool is not used).
+// Blocks are bucketed — powers of two up to 1 MiB, then steps of 1/8 of the
+// size's power of two (>= 2 MiB) — and recycled on the connection's single
+// stream, so reuse is stream-ordered by construction.  Cached bytes above
+// kLimit are released after a stream synchronisation.
+struct DevicePool {
+  static constexpr size_t kLimit = (size_t)64 << 30;
+  std::map<size_t, std::vector<void *>> free_;
+  size_t cached = 0;
+  hipStream_t s = nullptr;
+  int device = 0;
+  void Free(void *p) { (void)hipFree(p); }
+  static size_t Bucket(size_t bytes) {
+    if (bytes <= 256) return 256;
+    size_t p2 = 256;
+    while (p2 < bytes) p2 <<= 1;
+    if (p2 <= ((size_t)1 << 20)) return p2;
+    size_t step = std::max<size_t>(p2 / 16, (size_t)2 << 20);  // p2/2 < bytes <= p2: steps of p2/16 = (1/8 of floor pow2)
+    return (bytes + step - 1) / step * step;
+  }
+  void ReleaseAll() {
+    if (s) (void)hipStreamSynchronize(s);
+    for (auto &kv : free_)
+      for (void *p : kv.second) Free(p);
+    free_.clear();
+    cached = 0;
+  }
+  void *Get(size_t b) {
+    auto it = free_.find(b);
+    if (it != free_.end() && !it->second.empty()) {
+      void *p = it->second.back();
+      it->second.pop_back();
+      cached -= b;
+      return p;
+    }
+    void *p = nullptr;
+    if (hipMalloc(&p, b) != hipSuccess) {
+      (void)hipGetLastError();
+      ReleaseAll();  // give cached blocks back and retry once
+      if (hipMalloc(&p, b) != hipSuccess) {
+        (void)hipGetLastError();
+        return nullptr;
+      }
+    }
+    return p;
+  }
+  void Put(size_t b, void *p) {
+    if (cached + b > kLimit) {
+      if (s) (void)hipStreamSynchronize(s);
+      Free(p);
+      return;
+    }
+    free_[b].push_back(p);
+    cached += b;
+  }
+  ~DevicePool() { ReleaseAll(); }
+};
+
+struct Engine {
+  int device = 0;
+  std::shared_ptr<DevicePool> pool;
+  bool has_gpu = false;
+  hipStream_t stream = nullptr;
+  int32_t *d_err = nullptr;
+  int64_t *d_scratch = nullptr;  // small device scratch (counts)
+  // select_rounds control block (abort word, total, {count, epoch} granules):
+  // zeroed when (re)allocated, then reused with a fresh epoch per launch
+  unsigned long long *d_rounds = nullptr;
+  size_t rounds_bytes = 0;
+  uint32_t rounds_epoch = 0;
+  void *d_small = nullptr;       // 64 KB scratch for small states
+  dev::AggPartial *d_partials = nullptr;  // per-workgroup partials of the fused filter-aggregate
+  const void *defer_count_for = nullptr;  // the top-level BoundSelect whose GROUP BY count may stay on the device
+  // pinned host staging for small results: every D2H of a query lands here
+  // and the query pays ONE stream synchronisation
+  // set around the query of CREATE TABLE AS / INSERT ... SELECT: select_rounds
+  // then also returns its outputs' zone maps (DCol::zn), so the append needs no
+  // statistics pass
+  bool want_zone_maps = false;
+  uint8_t *h_pinned = nullptr;
+  size_t h_pinned_bytes = 0;
+  // grows the arena (power of two, up to kPinnedMax) so a query result of
+  // that size still lands in pinned memory with one synchronisation
+  static constexpr size_t kPinnedMax = (size_t)512 << 20;
+  bool EnsurePinned(size_t need) {
+    if (need <= h_pinned_bytes) return true;
+    if (need > kPinnedMax) return false;
+    size_t b = h_pinned_bytes ? h_pinned_bytes : 1 << 20;
+    while (b < need) b <<= 1;
+    HIPCHK(hipStreamSynchronize(stream));
+    if (h_pinned) HIPCHK(hipHostFree(h_pinned));
+    h_pinned = nullptr;
+    h_pinned_bytes = 0;
+    HIPCHK(hipHostMalloc((void **)&h_pinned, b, hipHostMallocDefault));
+    h_pinned_bytes = b;
+    return true;
+  }
+  // coherent pinned buffer for small results, written by host_copy_kernel
+  static constexpr size_t kMappedBytes = (size_t)64 << 10;
+  uint8_t *h_mapped = nullptr;
+  // H2D ingest ring: host rows are copied into a pinned slot while the DMA of
+  // the previous slot runs (bulk appender path)
+  static constexpr int kStageSlots = 4;
+  static constexpr size_t kStageBytes = (size_t)16 << 20;
+  uint8_t *h_stage[kStageSlots] = {nullptr, nullptr, nullptr, nullptr};
+  hipEvent_t stage_ev[kStageSlots] = {nullptr, nullptr, nullptr, nullptr};
+  // zone-map statistics of appends still in flight (appender's pinned double
+  // buffer): the stats reduction's 3 values land in a pinned slot and are
+  // folded into the column by SettlePending before the next device statement
+  struct PendingStat {
+    DevColumn *col;
+    long long *h;  // pinned: min, max, non-null count
+    int64_t n;
+    bool first_rows;
+    int64_t rows;  // the table's row count after this append
+  };
+  std::vector<PendingStat> pending_stats;
+  std::vector<long long *> stat_slots;  // free pinned 3-value slots
+  // an async append's DMA from a pinned appender buffer is in flight: the next
+  // SettlePending waits for it, so the buffer is never refilled under the DMA
+  bool inflight_h2d = false;
+  // select_rounds outcomes (duckdb_mbx_engine_stats): launches, launches that
+  // gave up because a workgroup was never scheduled (the two-pass form reran
+  // the query), launches that failed to start
+  int64_t sr_launches = 0, sr_aborts = 0, sr_launch_failures = 0;
+  // the connection's mbx_scan_codes / mbx_scan_codes_min_rows (set by Eng)
+  bool scan_codes = true;
+  int64_t scan_codes_min_rows = 0;
+  bool profile = false;
+  std::vector<ProfEvent> events;
+  // kernels timed on shard engines during this query (gpu_devices)
+  std::mutex shard_mu;
+  std::vector<QueryProfile::Kernel> shard_kernels;
+  std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool;  // reused across queries
+  size_t ev_used = 0;
+  // The per-kernel profile's event pairs: timing only (FinishProfile reads them
+  // after a stream synchronisation), so without the system-scope fence a
+  // recorded event otherwise performs (an L2 writeback and invalidate around
+  // each timestamp, which also delays the next launch on the stream)
+  std::pair<hipEvent_t, hipEvent_t> NextEvents() {
+    if (ev_used == ev_pool.size()) {
+      hipEvent_t a, b;
+      (void)hipEventCreateWithFlags(&a, hipEventDisableSystemFence);
+      (void)hipEventCreateWithFlags(&b, hipEventDisableSystemFence);
+      ev_pool.push_back({a, b});
+    }
+    return ev_pool[ev_used++];
+  }
+  ~Engine() {
+    if (has_gpu) {
+      hipSetDevice(device);
+      if (stream) hipStreamSynchronize(stream);
+      pool->s = nullptr;  // tables may hold pool blocks past this engine (adopted results)
+      pool.reset();       // returns cached buffers before the stream goes away
+      for (auto &e : ev_pool) {
+        hipEventDestroy(e.first);
+        hipEventDestroy(e.second);
+      }
+      if (d_err) hipFree(d_err);
+      if (d_scratch) hipFree(d_scratch);
+      if (d_rounds) hipFree(d_rounds);
+      if (d_small) hipFree(d_small);
+      if (d_partials) hipFree(d_partials);
+      if (h_pinned) hipHostFree(h_pinned);
+      if (h_mapped) hipHostFree(h_mapped);
+      for (auto &ps : pending_stats) stat_slots.push_back(ps.h);
+      for (auto *h : stat_slots) hipHostFree(h);
+      for (int i = 0; i < kStageSlots; i++) {
+        if (h_stage[i]) hipHostFree(h_stage[i]);
+        if (stage_ev[i]) hipEventDestroy(stage_ev[i]);
+      }
+      if (stream) hipStreamDestroy(stream);
+    }
+  }
+};
+
+struct ProfScope {
+  Engine &e;
+  bool on;
+  size_t idx;
+  ProfScope(Engine &en, const char *name, double bytes, int64_t rows) : e(en), on(en.profile) {
+    if (!on) return;
+    ProfEvent pe;
+    pe.name = name;
+    pe.bytes = bytes;
+    pe.rows = rows;
+    auto ev = e.NextEvents();
+    pe.a = ev.first;
+    pe.b = ev.second;
+    hipEventRecord(pe.a, e.stream);
+    e.events.push_back(pe);
+    idx = e.events.size() - 1;
+  }
+  ~ProfScope() {
+    if (on) hipEventRecord(e.events[idx].b, e.stream);
+  }
+};
+
+// ---------------------------------------------------------------------------
+// device buffers and relations
+// ---------------------------------------------------------------------------
+// Every intermediate device buffer comes from the connection's DevicePool
+// and returns to it when its last owner lets go.
+struct DevBuf {
+  void *p = nullptr;
+  size_t bytes = 0;
+  std::shared_ptr<DevicePool> pool;
+  ~DevBuf() {
+    if (p && pool) pool->Put(bytes, p);
+  }
+};
+typedef std::shared_ptr<DevBuf> DevBufPtr;
+
+struct DCol {
+  LogicalType type;
+  Phys phys = P_I64;
+  void *data = nullptr;
+  uint64_t *validity = nullptr;
+  int64_t *offsets = nullptr;  // strings
+  char *chars = nullptr;
+  int64_t chars_len = 0;
+  std::vector<DevBufPtr> owners;
+  // statistics when the column is a table column
+  const DevColumn *table_col = nullptr;
+  // the table column's buffer owners, when the data is read in place
+  std::vector<std::shared_ptr<void>> pins;
+  // zone map the producing kernel computed over its zn rows (select_rounds
+  // under Engine::want_zone_maps): min / max of the non-NULL values, their count
+  int64_t zn = -1, zvalid = 0;
+  i128 zmin = 0, zmax = 0;
+};
+
+struct DRel {
+  std::vector<DCol> cols;
+  int64_t n = 0;
+  bool range = false;  // column 0 is the virtual range column
+  int64_t rs = 0, rstep = 1;
+  // the row count is still on the device (n is its upper bound; the columns
+  // hold n rows): only the top-level aggregate of ExecuteSelect leaves it so,
+  // for ToHost to read with the rows in one copy; SettleCount otherwise
+  const int64_t *n_dev = nullptr;
+  std::shared_ptr<void> n_owner;
+};
+
+inline int64_t Words64(int64_t n) { return (n + 63) / 64; }
+
+// ---- executor.cpp
+Engine &Eng(Connection &c);
+void FoldStats(DevColumn &c, int64_t n, int64_t nvalid, i128 mn, i128 mx, bool first_rows);
+void SettlePending(Engine &e);
+DevBufPtr Alloc(Engine &e, size_t bytes, bool zero = false);
+DCol ColFromTable(const DevColumn &c);
+void CheckError(Engine &e);
+void RaiseDeviceError(Engine &e, int32_t err);
+void SettleCount(Engine &e, DRel &r);
+void UploadHostColumn(Engine &e, const HostColumn &hc, int64_t n, DCol &d);
+DRel UploadRows(Engine &e, const std::vector<std::vector<Value>> &rows, const std::vector<LogicalType> &types);
+DCol AllocOut(Engine &e, const LogicalType &t, int64_t n, bool with_valid, bool zero_valid = true);
+DRel FilterProject(Engine &e, const DRel &rel, const BExprPtr &pred, const std::vector<BExprPtr> &exprs);
+const BExpr *StripWidening(const BExpr *x);
+bool RangePredicate(const BExpr &p, int *col, i128 *lo, i128 *hi);
+bool RangeConj(const BExpr &p, std::map<int, std::pair<i128, i128>> &ranges);
+bool FastIntCol(const DRel &rel, int c);
+DRel GatherRel(Engine &e, const DRel &r, const int64_t *perm, int64_t n);
+DRel ConcatRels(Engine &e, std::vector<DRel> &parts);
+ResultPtr ToHost(Engine &e, const DRel &r, const std::vector<std::string> &names, int64_t offset, int64_t limit,
+                 size_t ncols, bool text = false);
+DRel RunBranch(Engine &e, Connection &c, const BoundSelect &s);
+size_t VisibleCols(const BoundSelect &s);
+DRel RunSelectDev(Engine &e, Connection &c, const BoundSelect &s, bool top = false);
+bool IsHostConstantSelect(const BoundSelect &s);
+ResultPtr HostConstantSelect(const BoundSelect &s);
+void FinishProfile(Connection &c, Engine &e, double total_ms);
+// ---- aggregate.cpp
+DRel Aggregate(Engine &e, const DRel &src, const BoundSelect &s);
+// ---- ingest.cpp
+void UpdateScanCodes(Engine &e, DevColumn &c, int64_t nrows);
+void AppendCast(Engine &e, Table &t, DRel r, const std::vector<int> &col_map);
+// ---- sharded.cpp
+void KeyBytes(const Value &v, std::string &out);
+int CompareValues(const Value &a, const Value &b);
+DRel ShardedBranch(Engine &e, Connection &c, const BoundSelect &s);
+ResultPtr ShardedAggregateHost(Connection &c, const BoundSelect &s);
+int TargetPart(const Connection &c, const Table &t);
+void SyncRows(Table &t);
+void ShardedInsertSelect(Connection &c, Table &t, const BoundSelect &s, const std::vector<int> &col_map);
+
+template <typename T>
+T ReadDev(Engine &e, const void *p) {
+  // through the pinned arena: a pageable destination would take HIP's staged copy
+  static_assert(sizeof(T) <= 64, "small device words only");
+  HIPCHK(hipMemcpyAsync(e.h_pinned, p, sizeof(T), hipMemcpyDeviceToHost, e.stream));
+  HIPCHK(hipStreamSynchronize(e.stream));
+  T v;
+  memcpy(&v, e.h_pinned, sizeof(T));
+  return v;
+}
+
+}  // namespace mbx

@@ -3,7 +3,7 @@
 // Same names, parameter types, ownership and error conventions as the
 // reference shim /root/reference/src/duckdb_native.c (each function cites the
 // definition it replaces).  Instead of forwarding to libduckdb, statements go
-// to the MI355X engine (engine.cpp / executor.cpp / kernels.hip).
+// to the MI355X engine (engine.cpp / the executor units / kernels.hip).
 //
 // Deliberate differences (documented in DESIGN.md):
 //  * the last-error string is thread_local (reference: process-global static,

@@ -1,5 +1,5 @@
 // vm.h — the device expression program (shared by the host compiler in
-// executor.cpp and the tile interpreter in kernels.hip).
+// vm_compile.h and the tile interpreter in kernels.hip).
 //
 // A program evaluates scalar expressions for a tile of 256 rows at a time.
 // Registers live in LDS as [reg][row] planes (lo 64 bits, hi 64 bits, null

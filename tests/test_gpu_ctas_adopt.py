@@ -1,5 +1,5 @@
 """CREATE TABLE AS / INSERT ... SELECT into an empty table take over the
-query's output blocks (executor.cpp AdoptResultColumn) instead of allocating
+query's output blocks (ingest.cpp AdoptResultColumn) instead of allocating
 and copying.  These tests pin what must not change when they do: the values,
 the NULLs, the zone map (read by the planner for direct GROUP BY tables and
 narrow staging), later appends growing the adopted column, a result that
