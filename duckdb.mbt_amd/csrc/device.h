@@ -324,11 +324,11 @@ struct HashKeys {
 // tag | 40-bit representative row).  Produces slot_of_row in [0, ngroups)
 // (dense group ids in table order), rep_row[g], count_star[g] and
 // *ngroups (device).  Scratch: table (cap x 8 B), entry ids (cap x 4 B).
-// Scratch allocator the helpers below use (set per call by the executor to
-// the connection's caching pool; the helpers run on that connection's stream).
-typedef void *(*TempAllocFn)(size_t bytes, void *ctx);
-typedef void (*TempFreeFn)(void *p, size_t bytes, void *ctx);
-void SetTempAllocator(TempAllocFn a, TempFreeFn f, void *ctx);
+// Scratch the helpers below use: defined by the executor, which serves it from
+// the calling connection's caching pool (the helpers run on that connection's
+// stream).  TempAlloc throws when no pool is bound or the pool is exhausted.
+void *TempAlloc(size_t bytes);
+void TempFree(void *p, size_t bytes);
 void CountSlots(const int32_t *slot_of_row, int64_t n, unsigned long long *count_star, hipStream_t s);
 void HashGroupAssign(const HashKeys &k, int64_t n, unsigned long long *table, int64_t cap, int32_t *slot_of_row,
                      int32_t *gid_of_entry, int64_t *rep_row, unsigned long long *count_star, int64_t *ngroups,
@@ -412,15 +412,14 @@ void OffsetsU32(const int64_t *offsets, uint32_t *out, int64_t m, hipStream_t s)
 // x > 24.  A chunk is FC_CHUNK consecutive 256-row steps, owned by one wave in
 // both passes (so a wave's stores of a chunk form one contiguous run).
 //  1. FilterCountChunks: predicate columns through an LDS-DMA ring; one
-//     uint32 count per K1 steps (no per-row bits; K1 = FC_CHUNK by default,
-//     one count per chunk), the partial last step's count in counts[CountEntries].
-//  2. ScanTileCounts over CountEntries + 1 entries -> offsets and the total.
+//     uint32 count per chunk (no per-row bits), the partial last step's count
+//     in counts[CountChunks].
+//  2. ScanTileCounts over CountChunks + 1 entries -> offsets and the total.
 //  3. CompactRecompute: output columns through an LDS-DMA ring; the predicates
 //     are evaluated again on the loaded slices (no bits to read), each selected
 //     row goes to offsets[chunk] + its rank in the chunk.
 #define FC_CHUNK 8
-int64_t CountChunks(int64_t nrows);   // pass-2 chunks of full steps
-int64_t CountEntries(int64_t nrows);  // pass-1 count entries (the count array has one more)
+int64_t CountChunks(int64_t nrows);  // chunks of full steps (the count array has one more entry)
 void FilterCountChunks(const FilterMultiDesc &d, int64_t nrows, uint32_t *counts, hipStream_t s);
 void CompactRecompute(const CompactDesc &d, int64_t nrows, const int64_t *chunk_offsets, hipStream_t s);
 

@@ -39,12 +39,15 @@ int DeviceCount() {
 
 // scratch for the device helpers (hipcub temp storage, hash flags) from the
 // calling connection's pool
-static void *TempAllocCb(size_t bytes, void *ctx) {
-  DevicePool *p = (DevicePool *)ctx;
-  return p->Get(DevicePool::Bucket(bytes ? bytes : 16));
+static thread_local DevicePool *g_temp_pool = nullptr;
+void *dev::TempAlloc(size_t bytes) {
+  if (!g_temp_pool) throw std::runtime_error("device scratch allocator not set");
+  void *p = g_temp_pool->Get(DevicePool::Bucket(bytes ? bytes : 16));
+  if (!p) throw std::runtime_error("device scratch allocation failed");
+  return p;
 }
-static void TempFreeCb(void *ptr, size_t bytes, void *ctx) {
-  if (ptr) ((DevicePool *)ctx)->Put(DevicePool::Bucket(bytes ? bytes : 16), ptr);
+void dev::TempFree(void *ptr, size_t bytes) {
+  if (ptr && g_temp_pool) g_temp_pool->Put(DevicePool::Bucket(bytes ? bytes : 16), ptr);
 }
 
 std::shared_ptr<Engine> CreateEngine(int device, bool allow_no_gpu) {
@@ -64,7 +67,7 @@ std::shared_ptr<Engine> CreateEngine(int device, bool allow_no_gpu) {
   e->pool = std::make_shared<DevicePool>();
   e->pool->s = e->stream;
   e->pool->device = device;
-  dev::SetTempAllocator(&TempAllocCb, &TempFreeCb, e->pool.get());
+  g_temp_pool = e->pool.get();
   HIPCHK(hipMalloc(&e->d_err, 256));
   HIPCHK(hipMalloc(&e->d_scratch, 4096));
   HIPCHK(hipMalloc(&e->d_small, 1 << 16));
@@ -119,7 +122,7 @@ Engine &Eng(Connection &c) {
   if (!e.has_gpu)
     ThrowError("IO", "this statement reads table rows and needs the MI355X device, but no GPU is available");
   hipSetDevice(e.device);
-  dev::SetTempAllocator(&TempAllocCb, &TempFreeCb, e.pool.get());
+  g_temp_pool = e.pool.get();
   e.scan_codes = c.opts.scan_codes;
   e.scan_codes_min_rows = c.opts.scan_codes_min_rows;
   SettlePending(e);  // a statement never sees a column before its appended stats
@@ -800,7 +803,7 @@ static bool TryCountFirst(Engine &e, const DRel &rel, const dev::FilterMultiDesc
     C.npred++;
   }
   const int64_t n = rel.n;
-  const int64_t chunks = dev::CountEntries(n);
+  const int64_t chunks = dev::CountChunks(n);
   auto counts = Alloc(e, (size_t)(chunks + 1) * 4);
   auto offs = Alloc(e, (size_t)(chunks + 1) * 8);
   double pbytes = 0;

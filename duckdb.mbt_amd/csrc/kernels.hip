@@ -56,24 +56,6 @@ __device__ __forceinline__ void clk_stamp(int part) {
 namespace mbx {
 namespace dev {
 
-static thread_local TempAllocFn g_talloc = nullptr;
-static thread_local TempFreeFn g_tfree = nullptr;
-static thread_local void *g_tctx = nullptr;
-void SetTempAllocator(TempAllocFn a, TempFreeFn f, void *ctx) {
-  g_talloc = a;
-  g_tfree = f;
-  g_tctx = ctx;
-}
-static void *TempAlloc(size_t bytes) {
-  if (!g_talloc) throw std::runtime_error("device scratch allocator not set");
-  void *p = g_talloc(bytes, g_tctx);
-  if (!p) throw std::runtime_error("device scratch allocation failed");
-  return p;
-}
-static void TempFree(void *p, size_t bytes) {
-  if (p && g_tfree) g_tfree(p, bytes, g_tctx);
-}
-
 typedef __int128 i128;
 typedef unsigned __int128 u128;
 
@@ -365,36 +347,9 @@ __device__ __forceinline__ void acc_block_commit(Acc &A, AggState *st, unsigned 
 
 typedef long long v2i64 __attribute__((ext_vector_type(2)));
 typedef int v4i32 __attribute__((ext_vector_type(4)));
-template <typename T, bool NT>
-struct Vec4;  // 4 consecutive elements through 16-byte loads (global_load_dwordx4)
-template <bool NT>
-struct Vec4<int64_t, NT> {
-  static __device__ __forceinline__ void load(const int64_t *__restrict__ p, int64_t g, int64_t v[4]) {
-    const v2i64 *q = (const v2i64 *)p + 2 * g;
-    v2i64 a, b;
-    if (NT) {
-      a = __builtin_nontemporal_load(q);
-      b = __builtin_nontemporal_load(q + 1);
-    } else {
-      a = q[0];
-      b = q[1];
-    }
-    v[0] = a.x; v[1] = a.y; v[2] = b.x; v[3] = b.y;
-  }
-};
-template <bool NT>
-struct Vec4<int32_t, NT> {
-  static __device__ __forceinline__ void load(const int32_t *__restrict__ p, int64_t g, int64_t v[4]) {
-    v4i32 a = NT ? __builtin_nontemporal_load((const v4i32 *)p + g) : ((const v4i32 *)p)[g];
-    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
-  }
-};
-
 // Row-pair loads: lane l of a wave reads rows {2l, 2l+1} of a 128-row wave
 // step, so ONE load instruction covers a contiguous 1 KiB (int64) or 512 B
-// (int32) with no holes — every cache line is requested once.  (Vec4 above
-// makes each lane read 32 contiguous bytes as two 16-B loads: each load then
-// spans 2 KiB with 16-B gaps and every line is requested twice.)
+// (int32) with no holes — every cache line is requested once.
 typedef int v2i32 __attribute__((ext_vector_type(2)));
 template <typename T, bool NT>
 struct Pair;
@@ -419,74 +374,18 @@ struct Pair<int32_t, NT> {
 
 __device__ __forceinline__ void acc_count(Acc &A, bool ok) { A.cnt += ok; }
 
-// MODE 0: aggregate over the predicate column; 1: over a second column;
-// 2: COUNT only (no sum/min/max work in the loop).
-// CHUNK: each workgroup streams one contiguous slice (vs a grid-stride sweep).
-template <typename TP, typename TA, int MODE, int UNROLL, bool NT, bool CHUNK>
-__global__ __launch_bounds__(256) void filter_agg_v4_kernel(const TP *__restrict__ p, const TA *__restrict__ a, int64_t n,
-                                                         int64_t lo, uint64_t span, AggState *st,
-                                                         unsigned long long *cstar) {
-  Acc A;
-  A.cnt = 0; A.slo = 0; A.shi = 0; A.mn = INT64_MAX; A.mx = INT64_MIN;
-  const int64_t ngroups = n >> 2;  // groups of 4 elements
-  int64_t g, gend, stride;
-  if (CHUNK) {
-    const int64_t per = (ngroups + gridDim.x - 1) / gridDim.x;
-    g = (int64_t)blockIdx.x * per + threadIdx.x;
-    gend = (int64_t)blockIdx.x * per + per;
-    if (gend > ngroups) gend = ngroups;
-    stride = blockDim.x;
-  } else {
-    g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    gend = ngroups;
-    stride = (int64_t)gridDim.x * blockDim.x;
-  }
-  for (; g + (UNROLL - 1) * stride < gend; g += UNROLL * stride) {
-    int64_t pv[UNROLL][4], av[UNROLL][4];
-#pragma unroll
-    for (int u = 0; u < UNROLL; u++) {
-      Vec4<TP, NT>::load(p, g + u * stride, pv[u]);
-      if (MODE == 1) Vec4<TA, NT>::load(a, g + u * stride, av[u]);
-    }
-#pragma unroll
-    for (int u = 0; u < UNROLL; u++)
-#pragma unroll
-      for (int e = 0; e < 4; e++) {
-        int64_t x = pv[u][e];
-        bool ok = (uint64_t)(x) - (uint64_t)(lo) <= span;
-        if (MODE == 2) acc_count(A, ok);
-        else if (MODE == 1) acc_add(A, ok, av[u][e]);
-        else acc_add(A, ok, x);
-      }
-  }
-  for (; g < gend; g += stride) {
-    int64_t pv[4], av[4];
-    Vec4<TP, NT>::load(p, g, pv);
-    if (MODE == 1) Vec4<TA, NT>::load(a, g, av);
-#pragma unroll
-    for (int e = 0; e < 4; e++) {
-      bool ok = (uint64_t)(pv[e]) - (uint64_t)(lo) <= span;
-      if (MODE == 2) acc_count(A, ok);
-      else acc_add(A, ok, MODE == 1 ? av[e] : pv[e]);
-    }
-  }
-  // tail (n % 4 elements): handled by the first threads of block 0
-  int64_t tail = (ngroups << 2) + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (tail < n) {
-    int64_t x = p[tail];
-    bool ok = (uint64_t)(x) - (uint64_t)(lo) <= span;
-    if (MODE == 2) acc_count(A, ok);
-    else acc_add(A, ok, MODE == 1 ? (int64_t)a[tail] : x);
-  }
-  acc_block_commit(A, MODE == 2 ? nullptr : st, cstar, true);
-}
-
-// Row-pair version (default): U pair-loads in flight per lane.  Grid-stride
-// over pairs, or one contiguous slice of pairs per workgroup (CHUNK).
-template <typename TP, typename TA, int MODE, int UNROLL, bool NT, bool CHUNK>
+// Register-load filter-aggregate for the one shape filter_agg_lds below does
+// not take: a predicate column and an aggregated column of different widths
+// (MODE 1, TP != TA).  UNROLL row-pair loads in flight per lane, non-temporal,
+// one contiguous slice of pairs per workgroup (CHUNK): the best register-load
+// shape of the sweep in profiles/r01_filter_sweep_lds.json.  The loop is
+// written for any MODE / CHUNK; the constants below pick the shape that runs.
+template <typename TP, typename TA>
 __global__ __launch_bounds__(256) void filter_agg_kernel(const TP *__restrict__ p, const TA *__restrict__ a, int64_t n,
                                                          int64_t lo, uint64_t span, AggState *st,
                                                          unsigned long long *cstar) {
+  constexpr int MODE = 1, UNROLL = 8;
+  constexpr bool NT = true, CHUNK = true;
   Acc A;
   A.cnt = 0; A.slo = 0; A.shi = 0; A.mn = INT64_MAX; A.mx = INT64_MIN;
   const int64_t npairs = n >> 1;
@@ -836,134 +735,8 @@ __global__ __launch_bounds__(256) void scan_encode_kernel(const T *__restrict__ 
 // then owns 4 consecutive rows of every column.  A NULL-able column adds its
 // step's 4 validity words (one exec-masked LDS-DMA instruction); a row counts
 // only where every such column is non-NULL (the host admits a NULL-able
-// aggregated column only where that is the SQL answer).  NI = LDS-DMA
-// instructions per step (compile time: the counted vmcnt wait).
-template <int NI, int DEPTH>
-__global__ __launch_bounds__(256) void filter_multi_lds_kernel(FilterMultiDesc D, int64_t n, AggPartial *partials,
-                                                               int slot_bytes) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char fm_lds[];
-  const int SB = slot_bytes;
-  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  unsigned char *ring = fm_lds + (size_t)w * DEPTH * SB;
-  int off[FM_MAX], voff[FM_MAX];
-  {
-    int o = 0;
-#pragma unroll
-    for (int c = 0; c < FM_MAX; c++) {
-      off[c] = o;
-      if (c < D.ncol) o += D.col[c].phys == P_I64 ? 2048 : 1024;
-    }
-#pragma unroll
-    for (int c = 0; c < FM_MAX; c++) {
-      voff[c] = o;
-      if (c < D.ncol && D.col[c].valid) o += 32;
-    }
-  }
-  const int64_t nsteps = n >> 8;
-  const int64_t nw = (int64_t)gridDim.x * 4;
-  int64_t st = (int64_t)blockIdx.x * 4 + w;
-  auto issue = [&](int64_t q, int d) {
-    unsigned char *dst = ring + d * SB;
-#pragma unroll
-    for (int c = 0; c < FM_MAX; c++) {
-      if (c >= D.ncol) break;
-      const int B = D.col[c].phys == P_I64 ? 2048 : 1024;
-      const unsigned char *src = (const unsigned char *)D.col[c].data + q * B;
-      __builtin_amdgcn_global_load_lds((const void *)(src + lane * 16), (void *)(dst + off[c]), 16, 0, 2);
-      if (B == 2048)
-        __builtin_amdgcn_global_load_lds((const void *)(src + 1024 + lane * 16), (void *)(dst + off[c] + 1024), 16, 0, 2);
-      if (D.col[c].valid && lane < 2)
-        __builtin_amdgcn_global_load_lds((const void *)(D.col[c].valid + q * 4 + lane * 2), (void *)(dst + voff[c]), 16,
-                                         0, 0);
-    }
-  };
-  Acc A;
-  A.cnt = 0; A.slo = 0; A.shi = 0; A.mn = INT64_MAX; A.mx = INT64_MIN;
-  const bool mm32 = D.mm && D.mm32, mm = D.mm && !mm32, narrow = D.narrow;
-  int32_t mn32 = INT32_MAX, mx32 = INT32_MIN;
-  auto row = [&](bool ok, int64_t val) {
-    acc_row(A, ok, val, mm, narrow);
-    if (mm32) {
-      mn32 = min(mn32, ok ? (int32_t)val : INT32_MAX);
-      mx32 = max(mx32, ok ? (int32_t)val : INT32_MIN);
-    }
-  };
-  if (nsteps > 0) {
-#pragma unroll
-    for (int d = 0; d < DEPTH; d++) {
-      int64_t q = st + d * nw;
-      issue(q < nsteps ? q : 0, d);
-    }
-  }
-  int k = 0;
-  for (; st < nsteps; st += nw) {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NI * (DEPTH - 1)) : "memory");
-    const unsigned char *src = ring + k * SB;
-    int64_t v[FM_MAX][4];
-    unsigned vm = 0xFu;  // rows 4 lane + e where every NULL-able column is valid
-#pragma unroll
-    for (int c = 0; c < FM_MAX; c++) {
-      if (c >= D.ncol) break;
-      if (D.col[c].phys == P_I64) {
-        v2i64 x0 = *(const v2i64 *)(src + off[c] + lane * 32), x1 = *(const v2i64 *)(src + off[c] + lane * 32 + 16);
-        v[c][0] = x0.x; v[c][1] = x0.y; v[c][2] = x1.x; v[c][3] = x1.y;
-      } else {
-        v4i32 x = *(const v4i32 *)(src + off[c] + lane * 16);
-        v[c][0] = x.x; v[c][1] = x.y; v[c][2] = x.z; v[c][3] = x.w;
-      }
-      if (D.col[c].valid)
-        vm &= (unsigned)(*(const uint64_t *)(src + voff[c] + (lane >> 4) * 8) >> (4 * (lane & 15))) & 0xFu;
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    int64_t q = st + DEPTH * nw;
-    issue(q < nsteps ? q : st, k);
-#pragma unroll
-    for (int e = 0; e < 4; e++) {
-      bool ok = (vm >> e) & 1u;
-#pragma unroll
-      for (int c = 0; c < FM_MAX; c++)
-        if (c < D.ncol && D.col[c].is_pred) ok = ok && (uint64_t)(v[c][e]) - (uint64_t)(D.col[c].lo) <= D.col[c].span;
-      int64_t val = 0;
-#pragma unroll
-      for (int c = 0; c < FM_MAX; c++)
-        if (c == D.agg) val = v[c][e];
-      if (D.agg < 0) acc_count(A, ok);
-      else row(ok, val);
-    }
-    k = k + 1 == DEPTH ? 0 : k + 1;
-  }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  if (blockIdx.x == 0 && w == 0) {
-    for (int64_t i = (nsteps << 8) + lane; i < n; i += 64) {
-      bool ok = true;
-      int64_t val = 0;
-      for (int c = 0; c < D.ncol; c++) {
-        int64_t x = D.col[c].phys == P_I64 ? ((const int64_t *)D.col[c].data)[i] : (int64_t)((const int32_t *)D.col[c].data)[i];
-        if (D.col[c].is_pred) ok = ok && (uint64_t)(x) - (uint64_t)(D.col[c].lo) <= D.col[c].span;
-        if (D.col[c].valid) ok = ok && ((D.col[c].valid[i >> 6] >> (i & 63)) & 1);
-        if (c == D.agg) val = x;
-      }
-      if (D.agg < 0) acc_count(A, ok);
-      else row(ok, val);
-    }
-  }
-  if (mm32) {  // a count of 0 makes the emit write NULL whatever these hold
-    A.mn = mn32;
-    A.mx = mx32;
-  }
-  if (narrow) A.shi = (int64_t)A.slo >> 63;
-  acc_wave_reduce(A);
-  __syncthreads();
-  Acc *part = (Acc *)fm_lds;
-  if (lane == 0) part[w] = A;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    Acc T0 = part[0];
-    for (int i = 1; i < 4; i++) acc_merge(T0, part[i]);
-    partials[blockIdx.x] = AggPartial{T0.cnt, T0.slo, T0.shi, T0.mn, T0.mx};
-  }
-}
-
+// aggregated column only where that is the SQL answer).
+//
 // Compile-time layout of filter_multi_t: NC columns, bit c of WM = column c is
 // 8 bytes wide (else 4); slices at fixed offsets, then the NULL-able columns'
 // 32-B validity words (runtime: which columns, at the end of the slot).
@@ -978,13 +751,14 @@ __device__ __forceinline__ void fm_wait() {
   asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 
-// filter_multi_lds with the column layout as template parameters (the
-// generic kernel above decides widths and predicate roles per column and row
-// at run time: ≈865 instructions in its loop region, exec-mask branches for
-// each short-circuit, SGPR spills).  Here every slice read has a fixed offset
-// and width, predicates combine bitwise, and only the NULL-able columns
-// (0..NC, their validity words one exec-masked LDS-DMA instruction each) stay
-// run-time: a scalar switch picks the exact counted vmcnt for their number.
+// The column layout is a template parameter (a kernel that decided widths and
+// predicate roles per column and row at run time had ≈865 instructions in its
+// loop region, exec-mask branches for each short-circuit and SGPR spills; it
+// won on no shape, profiles/r02_filter_multi_templated.log, and was
+// removed).  Every slice read has a fixed offset and width, predicates
+// combine bitwise, and only the NULL-able columns (0..NC, their validity
+// words one exec-masked LDS-DMA instruction each) stay run-time: a scalar
+// switch picks the exact counted vmcnt for their number.
 // The host puts the aggregated column first and gives every column that is
 // not a predicate the always-true range [INT64_MIN, +2^64), so a row's test
 // is the same branch-free compare for every column.  MODE: 0 COUNT only,
@@ -1137,60 +911,39 @@ __global__ __launch_bounds__(256) void filter_multi_t_kernel(FilterMultiDesc D, 
 }
 
 namespace {
+// Ring depth by the columns' LDS-DMA instructions per step: 6 for one, 3 for
+// two, 2 above (profiles/r02_filter_multi_sweep.log).
 template <int NC, int WM, int MODE>
-void FmtLaunchM(const FilterMultiDesc &d, int64_t nrows, AggPartial *partials, int slot, int grid, int dp,
-                hipStream_t s) {
+void FmtLaunchM(const FilterMultiDesc &d, int64_t nrows, AggPartial *partials, int slot, int grid, hipStream_t s) {
   constexpr int ni = FmCols<NC, WM>::ni();
-  if constexpr (ni <= 1) {
-    hipLaunchKernelGGL((filter_multi_t_kernel<NC, WM, 6, MODE>), dim3(grid), dim3(256), (size_t)4 * 6 * slot, s, d,
-                       nrows, partials, slot);
-  } else if constexpr (ni == 2) {
-    hipLaunchKernelGGL((filter_multi_t_kernel<NC, WM, 3, MODE>), dim3(grid), dim3(256), (size_t)4 * 3 * slot, s, d,
-                       nrows, partials, slot);
-  } else {
-    if (dp == 3)
-      hipLaunchKernelGGL((filter_multi_t_kernel<NC, WM, 3, MODE>), dim3(grid), dim3(256), (size_t)4 * 3 * slot, s, d,
-                         nrows, partials, slot);
-    else
-      hipLaunchKernelGGL((filter_multi_t_kernel<NC, WM, 2, MODE>), dim3(grid), dim3(256), (size_t)4 * 2 * slot, s, d,
-                         nrows, partials, slot);
-  }
+  constexpr int DP = ni <= 1 ? 6 : ni == 2 ? 3 : 2;
+  hipLaunchKernelGGL((filter_multi_t_kernel<NC, WM, DP, MODE>), dim3(grid), dim3(256), (size_t)4 * DP * slot, s, d,
+                     nrows, partials, slot);
 }
 template <int NC, int WM>
-void FmtLaunch(const FilterMultiDesc &d, int mode, int64_t nrows, AggPartial *partials, int slot, int grid, int dp,
+void FmtLaunch(const FilterMultiDesc &d, int mode, int64_t nrows, AggPartial *partials, int slot, int grid,
                hipStream_t s) {
-  if (mode == 0) FmtLaunchM<NC, WM, 0>(d, nrows, partials, slot, grid, dp, s);
-  else if (mode == 1) FmtLaunchM<NC, WM, 1>(d, nrows, partials, slot, grid, dp, s);
-  else if (mode == 3) FmtLaunchM<NC, WM, 3>(d, nrows, partials, slot, grid, dp, s);
-  else FmtLaunchM<NC, WM, 2>(d, nrows, partials, slot, grid, dp, s);
+  if (mode == 0) FmtLaunchM<NC, WM, 0>(d, nrows, partials, slot, grid, s);
+  else if (mode == 1) FmtLaunchM<NC, WM, 1>(d, nrows, partials, slot, grid, s);
+  else if (mode == 3) FmtLaunchM<NC, WM, 3>(d, nrows, partials, slot, grid, s);
+  else FmtLaunchM<NC, WM, 2>(d, nrows, partials, slot, grid, s);
 }
 template <int NC, int WM = 0>
 void FmtDispatch(const FilterMultiDesc &d, int wm, int mode, int64_t nrows, AggPartial *partials, int slot, int grid,
-                 int dp, hipStream_t s) {
+                 hipStream_t s) {
   if constexpr (WM < (1 << NC)) {
-    if (wm == WM) return FmtLaunch<NC, WM>(d, mode, nrows, partials, slot, grid, dp, s);
-    FmtDispatch<NC, WM + 1>(d, wm, mode, nrows, partials, slot, grid, dp, s);
+    if (wm == WM) return FmtLaunch<NC, WM>(d, mode, nrows, partials, slot, grid, s);
+    FmtDispatch<NC, WM + 1>(d, wm, mode, nrows, partials, slot, grid, s);
   }
 }
 }  // namespace
 
 int FilterMultiPartials(const FilterMultiDesc &d_in, int64_t nrows, AggPartial *partials, hipStream_t s) {
   FilterMultiDesc d = d_in;
-  int nld = 0, slot = 0;  // nld: LDS-DMA instructions per step (the executor keeps it <= 8)
-  for (int c = 0; c < d.ncol; c++) {
-    nld += d.col[c].phys == P_I64 ? 2 : 1;
-    slot += d.col[c].phys == P_I64 ? 2048 : 1024;
-    if (d.col[c].valid) {
-      nld++;
-      slot += 32;
-    }
-  }
+  if (d.ncol < 1 || d.ncol > FM_MAX) throw std::runtime_error("FilterMultiPartials: shape");
+  int slot = 0;
+  for (int c = 0; c < d.ncol; c++) slot += (d.col[c].phys == P_I64 ? 2048 : 1024) + (d.col[c].valid ? 32 : 0);
   slot = (slot + 15) & ~15;
-  // MBX_FM_DEPTH=<2..4>: ring depth for 3..5 loads per step (sweeps)
-  int dp = 2;
-  if (const char *ed = Knob("MBX_FM_DEPTH")) dp = atoi(ed) >= 2 && atoi(ed) <= 4 ? atoi(ed) : 2;
-  const char *ev = Knob("MBX_FM_VARIANT");
-  const bool templ = !(ev && strcmp(ev, "generic") == 0) && d.ncol >= 1 && d.ncol <= 4 && (dp == 2 || dp == 3);
   int grid = 0;
   auto plan = [&](int gpc) {
     grid = NumCUs() * gpc;
@@ -1206,64 +959,38 @@ int FilterMultiPartials(const FilterMultiDesc &d_in, int64_t nrows, AggPartial *
     d.mm32 = d.mm && d.narrow && d.maxabs < ((uint64_t)1 << 31) && !(e32 && e32[0] == '0');
   };
   auto mode_of = [&] { return d.agg < 0 ? 0 : (!d.mm && d.narrow) ? 1 : (d.mm32 && d.narrow) ? 3 : 2; };
-  // Workgroups per CU: the generic kernel 3 (3.39 ms vs 3.79 at 2 for 1e9
-  // rows of (x i64, k i32, v i64), profiles/r01_filter_multi_sweep.log); the
-  // templated one 1 for its compile-time modes (COUNT, narrow SUM, narrow SUM
-  // + int32 MIN/MAX) and 3 for the general mode and one-column SUMs
+  // Workgroups per CU: 1 for the compile-time modes (COUNT, narrow SUM, narrow
+  // SUM + int32 MIN/MAX) and 3 for the general mode and one-column SUMs
   // (profiles/r02_filter_multi_modes.log).
   const char *e = Knob("MBX_FM_BLOCKS_PER_CU");
   const int gpc_env = e && *e ? atoi(e) : 0;
   if (gpc_env > 0) {
     plan(gpc_env);
-  } else if (!templ) {
-    plan(3);
   } else {
     plan(1);
     const int m1 = mode_of();
     if (m1 == 2 || (m1 == 1 && d.ncol == 1)) plan(3);
   }
-#define FM(L, DP)                                                                                            \
-  hipLaunchKernelGGL((filter_multi_lds_kernel<L, DP>), dim3(grid), dim3(256), (size_t)4 * DP * slot, s, d, nrows, \
-                     partials, slot)
-  // the templated kernel (MBX_FM_VARIANT=generic keeps the one below)
-  if (templ) {
-    FilterMultiDesc t = d;  // aggregated column first; non-predicates always true
-    if (t.agg > 0) {
-      std::swap(t.col[0], t.col[t.agg]);
-      t.agg = 0;
-    }
-    for (int c = 0; c < t.ncol; c++)
-      if (!t.col[c].is_pred) {
-        t.col[c].lo = INT64_MIN;
-        t.col[c].span = ~0ull;
-      }
-    const int mode = mode_of();
-    int wm = 0;
-    for (int c = 0; c < t.ncol; c++)
-      if (t.col[c].phys == P_I64) wm |= 1 << c;
-    switch (t.ncol) {
-      case 1: FmtDispatch<1>(t, wm, mode, nrows, partials, slot, grid, dp, s); break;
-      case 2: FmtDispatch<2>(t, wm, mode, nrows, partials, slot, grid, dp, s); break;
-      case 3: FmtDispatch<3>(t, wm, mode, nrows, partials, slot, grid, dp, s); break;
-      default: FmtDispatch<4>(t, wm, mode, nrows, partials, slot, grid, dp, s); break;
-    }
-    CHECK_LAUNCH();
-    return grid;
+  // aggregated column first; non-predicates always true
+  if (d.agg > 0) {
+    std::swap(d.col[0], d.col[d.agg]);
+    d.agg = 0;
   }
-#define FMD(L) \
-  if (dp == 2) FM(L, 2); else if (dp == 3) FM(L, 3); else FM(L, 4);
-  switch (nld) {
-    case 1: FM(1, 6); break;
-    case 2: FM(2, 3); break;
-    case 3: FMD(3); break;
-    case 4: FMD(4); break;
-    case 5: FMD(5); break;
-    case 6: FM(6, 2); break;
-    case 7: FM(7, 2); break;
-    default: FM(8, 2); break;
+  for (int c = 0; c < d.ncol; c++)
+    if (!d.col[c].is_pred) {
+      d.col[c].lo = INT64_MIN;
+      d.col[c].span = ~0ull;
+    }
+  const int mode = mode_of();
+  int wm = 0;
+  for (int c = 0; c < d.ncol; c++)
+    if (d.col[c].phys == P_I64) wm |= 1 << c;
+  switch (d.ncol) {
+    case 1: FmtDispatch<1>(d, wm, mode, nrows, partials, slot, grid, s); break;
+    case 2: FmtDispatch<2>(d, wm, mode, nrows, partials, slot, grid, s); break;
+    case 3: FmtDispatch<3>(d, wm, mode, nrows, partials, slot, grid, s); break;
+    default: FmtDispatch<4>(d, wm, mode, nrows, partials, slot, grid, s); break;
   }
-#undef FMD
-#undef FM
   CHECK_LAUNCH();
   return grid;
 }
@@ -1304,105 +1031,46 @@ void InitAggStates(AggState *st, int64_t n, hipStream_t s) {
   CHECK_LAUNCH();
 }
 
-// Launch configuration of the fused filter-aggregate kernel.  The defaults
-// were chosen by the A/B sweep recorded in profiles/ (tools/sweep_filter.py);
-// MBX_FA_VARIANT="u<unroll>_<nt|pl>_<gs|ch>_g<blocks per CU>" overrides them
-// for experiments.
-struct FaVariant {
-  int unroll = 8;
-  bool nt = true;
-  bool chunk = true;
-  int blocks_per_cu = 1;
-  bool pairs = true;  // row-pair layout (false: the older 32-B-per-lane Vec4 layout)
-  int lds_depth = 6;  // >0: LDS-DMA ring of this depth per wave (blocks_per_cu then counts 256-thread blocks)
+// Fused filter-aggregate over one or two columns.  The LDS-DMA stream with 6
+// x 1 KiB slots per wave and one 256-thread workgroup per CU (one wave per
+// SIMD) takes every shape but one — 6.90 TB/s median on the 1e9-row COUNT vs
+// 6.80 at depth 8 and 6.06 for the best register-load shape
+// (profiles/r01_filter_sweep_lds.json, r01_filter_sweep_depth.json).  An
+// aggregated column of another width than the predicate column does not fit
+// its equal-width slots and runs filter_agg_kernel.
+struct FaLaunch {
+  bool mm;               // MIN/MAX requested
+  bool narrow;           // no lane's int64 partial sum can overflow (zone map)
+  bool mm32;             // MIN/MAX in int32 (zone map: |value| < 2^31)
+  AggPartial *partials;  // per-workgroup records, or nullptr: atomics into st / cstar
 };
 
-// Default: the LDS-DMA stream, 6 x 1 KiB slots per wave, one 256-thread
-// workgroup per CU (one wave per SIMD) — 6.90 TB/s median on the 1e9-row
-// COUNT vs 6.80 at depth 8 and 6.06 for the best register-load shape
-// (profiles/r01_filter_sweep_lds.json, r01_filter_sweep_depth.json).
-// MBX_FA_VARIANT overrides it: "d<depth>_g<blocks per CU>" (LDS-DMA) or
-// "u<unroll>_<nt|pl>_<gs|ch>_g<blocks per CU>[_v4]" (register loads).
-static FaVariant FaConfig(int mode) {
-  FaVariant v;
-  (void)mode;
-  const char *e = Knob("MBX_FA_VARIANT");
-  if (!e || !*e) return v;
-  int u = 8, g = 4;
-  char m1[8] = {0}, m2[8] = {0};
-  if (sscanf(e, "d%d_g%d", &u, &g) == 2) {
-    v.lds_depth = u;
-    v.blocks_per_cu = g;
-  } else if (sscanf(e, "u%d_%2s_%2s_g%d", &u, m1, m2, &g) == 4) {
-    v.lds_depth = 0;
-    v.unroll = u;
-    v.nt = m1[0] == 'n';
-    v.chunk = m2[0] == 'c';
-    v.blocks_per_cu = g;
-    v.pairs = strstr(e, "_v4") == nullptr;
-  }
-  return v;
-}
-
-static thread_local bool g_fa_pairs = true;
-static thread_local bool g_fa_mm = true, g_fa_narrow = false, g_fa_mm32 = false;  // per launch, set by FilterAggStates
-static thread_local AggPartial *g_fa_partials = nullptr;
-template <typename TP, typename TA, int MODE, int U, bool NT, bool CH>
-static void LaunchFA(const void *p, const void *a, int64_t n, int64_t lo, uint64_t span, AggState *st,
-                     unsigned long long *cstar, int grid, hipStream_t s) {
-  if (g_fa_pairs)
-    hipLaunchKernelGGL((filter_agg_kernel<TP, TA, MODE, U, NT, CH>), dim3(grid), dim3(256), 0, s, (const TP *)p,
-                       (const TA *)a, n, lo, span, st, cstar);
-  else
-    hipLaunchKernelGGL((filter_agg_v4_kernel<TP, TA, MODE, U, NT, CH>), dim3(grid), dim3(256), 0, s, (const TP *)p,
-                       (const TA *)a, n, lo, span, st, cstar);
-  CHECK_LAUNCH();
-}
-
-template <typename T, int MODE, int DEPTH>
-static void LaunchFALds(const void *p, const void *a, int64_t n, int64_t lo, uint64_t span, AggState *st,
-                        unsigned long long *cstar, int grid, hipStream_t s) {
-#define FAL(MM, NW)                                                                                                   \
-  hipLaunchKernelGGL((filter_agg_lds_kernel<T, MODE, DEPTH, MM, NW>), dim3(grid), dim3(256), 0, s, (const T *)p,   \
-                     (const T *)a, n, lo, span, st, cstar, g_fa_partials)
+template <typename T, int MODE>
+static void LaunchFALds(const FaLaunch &L, const void *p, const void *a, int64_t n, int64_t lo, uint64_t span,
+                        AggState *st, unsigned long long *cstar, int grid, hipStream_t s) {
+#define FAL(MM, NW)                                                                                         \
+  hipLaunchKernelGGL((filter_agg_lds_kernel<T, MODE, 6, MM, NW>), dim3(grid), dim3(256), 0, s, (const T *)p, \
+                     (const T *)a, n, lo, span, st, cstar, L.partials)
   if (MODE == 2) FAL(0, false);
-  else if (g_fa_mm) { if (g_fa_mm32) FAL(2, true); else if (g_fa_narrow) FAL(1, true); else FAL(1, false); }
-  else { if (g_fa_narrow) FAL(0, true); else FAL(0, false); }
+  else if (L.mm) { if (L.mm32) FAL(2, true); else if (L.narrow) FAL(1, true); else FAL(1, false); }
+  else { if (L.narrow) FAL(0, true); else FAL(0, false); }
 #undef FAL
   CHECK_LAUNCH();
 }
 
 // true when LaunchFilterAgg takes the LDS-DMA kernel for this shape
-static bool FaUsesLds(const FaVariant &v, int mode, int pphys, int aphys) {
-  return v.lds_depth > 0 && (mode != 1 || pphys == aphys);
-}
+static bool FaUsesLds(int mode, int pphys, int aphys) { return mode != 1 || pphys == aphys; }
 
 template <typename TP, typename TA, int MODE>
-static void LaunchFilterAgg(const FaVariant &v, const void *p, const void *a, int64_t n, int64_t lo, uint64_t span,
+static void LaunchFilterAgg(const FaLaunch &L, const void *p, const void *a, int64_t n, int64_t lo, uint64_t span,
                             AggState *st, unsigned long long *cstar, int grid, hipStream_t s) {
   if constexpr (MODE != 1 || sizeof(TP) == sizeof(TA)) {
-    if (v.lds_depth > 0) {
-      switch (v.lds_depth) {
-        case 1: case 2: case 3: case 4: LaunchFALds<TP, MODE, 4>(p, a, n, lo, span, st, cstar, grid, s); break;
-        case 5: LaunchFALds<TP, MODE, 5>(p, a, n, lo, span, st, cstar, grid, s); break;
-        case 6: LaunchFALds<TP, MODE, 6>(p, a, n, lo, span, st, cstar, grid, s); break;
-        case 7: LaunchFALds<TP, MODE, 7>(p, a, n, lo, span, st, cstar, grid, s); break;
-        case 8: LaunchFALds<TP, MODE, 8>(p, a, n, lo, span, st, cstar, grid, s); break;
-        default: LaunchFALds<TP, MODE, 16>(p, a, n, lo, span, st, cstar, grid, s); break;
-      }
-      return;
-    }
+    LaunchFALds<TP, MODE>(L, p, a, n, lo, span, st, cstar, grid, s);
+  } else {
+    hipLaunchKernelGGL((filter_agg_kernel<TP, TA>), dim3(grid), dim3(256), 0, s, (const TP *)p, (const TA *)a, n, lo,
+                       span, st, cstar);
+    CHECK_LAUNCH();
   }
-#define FA(U, NT, CH) LaunchFA<TP, TA, MODE, U, NT, CH>(p, a, n, lo, span, st, cstar, grid, s)
-#define FA_NTCH(U)                                          \
-  if (v.nt) { if (v.chunk) FA(U, true, true); else FA(U, true, false); } \
-  else { if (v.chunk) FA(U, false, true); else FA(U, false, false); }
-  if (v.unroll <= 1) { FA_NTCH(1) }
-  else if (v.unroll <= 2) { FA_NTCH(2) }
-  else if (v.unroll <= 4) { FA_NTCH(4) }
-  else { FA_NTCH(8) }
-#undef FA_NTCH
-#undef FA
 }
 
 int FilterAggStates(const void *pcol, int pphys, int64_t lo, int64_t hi, bool has_pred, const void *acol, int aphys,
@@ -1414,50 +1082,38 @@ int FilterAggStates(const void *pcol, int pphys, int64_t lo, int64_t hi, bool ha
   }
   uint64_t span = has_pred ? (uint64_t)hi - (uint64_t)lo : ~0ull;
   if (!has_pred) lo = INT64_MIN;
-  int mode = acol == nullptr ? 2 : (acol == pcol ? 0 : 1);
-  if (mode == 2) {
-    const char *cs = Knob("MBX_FA_COUNT_AS_SUM");  // experiment: COUNT through the SUM-shaped loop
-    if (cs && cs[0] == '1') {
-      mode = 0;
-      acol = pcol;
-      aphys = pphys;
-    }
-  }
-  FaVariant v = FaConfig(mode);
-  g_fa_pairs = v.pairs;
-  int grid = grid_blocks > 0 ? grid_blocks : NumCUs() * v.blocks_per_cu;
+  const int mode = acol == nullptr ? 2 : (acol == pcol ? 0 : 1);
+  int grid = grid_blocks > 0 ? grid_blocks : NumCUs();
   int64_t groups = (nrows >> 2) + 1;
   if (grid > groups) grid = (int)groups;
-  g_fa_mm = need_minmax;
-  const bool use_partials = partials && FaUsesLds(v, mode, pphys, aphys) && grid <= kMaxAggPartials;
-  g_fa_partials = use_partials ? partials : nullptr;
+  const bool use_partials = partials && FaUsesLds(mode, pphys, aphys) && grid <= kMaxAggPartials;
   if (!use_partials) InitAggStatesCounts(st, 1, cstar, 1, s);
+  FaLaunch L;
+  L.mm = need_minmax;
+  L.partials = use_partials ? partials : nullptr;
   // LDS-DMA kernel: a lane sees at most (ceil(pieces / waves) + 1) pieces of
   // 16 B, i.e. that many times 2 (int64) or 4 (int32) rows, tail included.
   {
-    const int asz = (mode == 1 ? aphys : pphys) == P_I64 ? 8 : 4;
     const int64_t rp = 64 * (16 / (pphys == P_I64 ? 8 : 4));
     const int64_t waves = (int64_t)grid * 4, pieces = nrows / rp;
     const int64_t rows_per_lane = ((pieces + waves - 1) / waves + 1) * (16 / (pphys == P_I64 ? 8 : 4));
-    (void)asz;
-    g_fa_narrow = sum_maxabs <= (uint64_t)INT64_MAX &&
-                  (unsigned __int128)sum_maxabs * (unsigned __int128)rows_per_lane < ((unsigned __int128)1 << 63);
+    L.narrow = sum_maxabs <= (uint64_t)INT64_MAX &&
+               (unsigned __int128)sum_maxabs * (unsigned __int128)rows_per_lane < ((unsigned __int128)1 << 63);
     // MIN/MAX in int32 when the zone map bounds |value| below 2^31 (MBX_FA_MM32=0 disables)
     const char *e32 = Knob("MBX_FA_MM32");
-    g_fa_mm32 = g_fa_narrow && sum_maxabs < ((uint64_t)1 << 31) && !(e32 && e32[0] == '0');
+    L.mm32 = L.narrow && sum_maxabs < ((uint64_t)1 << 31) && !(e32 && e32[0] == '0');
   }
   if (pphys == P_I64) {
-    if (mode == 0) LaunchFilterAgg<int64_t, int64_t, 0>(v, pcol, acol, nrows, lo, span, st, cstar, grid, s);
-    else if (mode == 2) LaunchFilterAgg<int64_t, int64_t, 2>(v, pcol, acol, nrows, lo, span, st, cstar, grid, s);
-    else if (aphys == P_I64) LaunchFilterAgg<int64_t, int64_t, 1>(v, pcol, acol, nrows, lo, span, st, cstar, grid, s);
-    else LaunchFilterAgg<int64_t, int32_t, 1>(v, pcol, acol, nrows, lo, span, st, cstar, grid, s);
+    if (mode == 0) LaunchFilterAgg<int64_t, int64_t, 0>(L, pcol, acol, nrows, lo, span, st, cstar, grid, s);
+    else if (mode == 2) LaunchFilterAgg<int64_t, int64_t, 2>(L, pcol, acol, nrows, lo, span, st, cstar, grid, s);
+    else if (aphys == P_I64) LaunchFilterAgg<int64_t, int64_t, 1>(L, pcol, acol, nrows, lo, span, st, cstar, grid, s);
+    else LaunchFilterAgg<int64_t, int32_t, 1>(L, pcol, acol, nrows, lo, span, st, cstar, grid, s);
   } else {
-    if (mode == 0) LaunchFilterAgg<int32_t, int32_t, 0>(v, pcol, acol, nrows, lo, span, st, cstar, grid, s);
-    else if (mode == 2) LaunchFilterAgg<int32_t, int32_t, 2>(v, pcol, acol, nrows, lo, span, st, cstar, grid, s);
-    else if (aphys == P_I64) LaunchFilterAgg<int32_t, int64_t, 1>(v, pcol, acol, nrows, lo, span, st, cstar, grid, s);
-    else LaunchFilterAgg<int32_t, int32_t, 1>(v, pcol, acol, nrows, lo, span, st, cstar, grid, s);
+    if (mode == 0) LaunchFilterAgg<int32_t, int32_t, 0>(L, pcol, acol, nrows, lo, span, st, cstar, grid, s);
+    else if (mode == 2) LaunchFilterAgg<int32_t, int32_t, 2>(L, pcol, acol, nrows, lo, span, st, cstar, grid, s);
+    else if (aphys == P_I64) LaunchFilterAgg<int32_t, int64_t, 1>(L, pcol, acol, nrows, lo, span, st, cstar, grid, s);
+    else LaunchFilterAgg<int32_t, int32_t, 1>(L, pcol, acol, nrows, lo, span, st, cstar, grid, s);
   }
-  g_fa_partials = nullptr;
   return use_partials ? grid : 0;
 }
 
@@ -2217,7 +1873,7 @@ bool GroupByDirectStates(const void *kcol, int kphys, int64_t kmin, int nk, cons
   if (const char *ex = Knob("MBX_GD_XCD")) pr.xcd = atoi(ex) != 0;
   // LDS-DMA variant: one flush at the end, so a block's whole row share must
   // fit the overflow bound the host derived (seg_rows) — else the segmented
-  // kernel below.  MBX_GD_VARIANT="d<depth>_g<blocks per CU>" / "seg".
+  // kernel below.  MBX_GD_VARIANT="d<2|3>_g<blocks per CU>" / "seg".
   // Defaults from profiles/r02_group_sweep.log (after the table atomics stopped
   // draining the DMA ring): d2_g1 for value aggregates (C3 1.735-1.77 ms, 2-6 %
   // under d2_g3 on two boxes) and d2_g3 for COUNT-only tables (0.56 ms vs 0.62
@@ -2247,14 +1903,13 @@ bool GroupByDirectStates(const void *kcol, int kphys, int64_t kmin, int nk, cons
       int64_t nsteps = nrows >> 8;
       int64_t waves = (int64_t)grid * 4;
       int64_t rows_per_block = ((nsteps + waves - 1) / waves) * 4 * 256 + 256;
-      if (vv && depth > 3) depth = 3;  // the validity form is built for 2- and 3-deep rings
       size_t tab = GroupDirectLds(nk, R, nv, mm, vm);
       size_t ring_off = (tab + 15) & ~(size_t)15;
       size_t slot = 256 * (size_t)(kphys == P_I64 ? 8 : 4) + (size_t)nv * 256 * (vphys == P_I64 ? 8 : 4) +
                     (vv ? 3 * 32 : 0);
       for (int j = 0; j < pr.n; j++)
         if (pr.p[j].src == 1) slot += 256 * (size_t)(pr.p[j].phys == P_I64 ? 8 : 4);
-      depth = depth <= 2 ? 2 : depth <= 3 ? 3 : depth <= 4 ? 4 : depth <= 6 ? 6 : 8;
+      depth = depth <= 2 ? 2 : 3;  // the kernel is built for 2- and 3-deep rings
       const size_t lds_cap = gpc <= 1 ? 150 * 1024 : gpc == 2 ? 76 * 1024 : 64 * 1024;
       size_t lds = ring_off + 4 * (size_t)depth * slot;
       // wide slots (predicate slices): trade table replicas for ring space;
@@ -2316,10 +1971,8 @@ bool GroupByDirectStates(const void *kcol, int kphys, int64_t kmin, int nk, cons
   hipLaunchKernelGGL((group_direct_lds_kernel<TK, TV, NV, MM, D, 0>), dim3(grid), dim3(256), lds, s,               \
                      (const TK *)kcol, (const TV *)v0, (const TV *)v1, nrows, kmin, nk, R, ring_off, cstar, st0,   \
                      st1, pr, gv, gpart);
-#define GLD(TK, TV, NV, MM)                                                                     \
-  if (depth == 2) { GL(TK, TV, NV, MM, 2) } else if (depth == 3) { GL(TK, TV, NV, MM, 3) }      \
-  else if (depth == 4) { GL(TK, TV, NV, MM, 4) } else if (depth == 6) { GL(TK, TV, NV, MM, 6) } \
-  else { GL(TK, TV, NV, MM, 8) }
+#define GLD(TK, TV, NV, MM) \
+  if (depth == 2) { GL(TK, TV, NV, MM, 2) } else { GL(TK, TV, NV, MM, 3) }
 #define GLV(TK, TV)                                                                      \
   if (nv == 0) { GLD(TK, TV, 0, false) }                                                 \
   else if (nv == 1) { if (mm) { GLD(TK, TV, 1, true) } else { GLD(TK, TV, 1, false) } } \
@@ -3617,24 +3270,19 @@ void FilterBits(const FilterMultiDesc &d, int64_t nrows, unsigned long long *bit
   int grid = NumCUs() * gpc;
   const int64_t need = (nrows >> 8) / 4 + 1;
   if (grid > need) grid = (int)need;
-  int dp = 0;  // MBX_FB_DEPTH: ring depth override (sweeps)
-  if (const char *e = Knob("MBX_FB_DEPTH")) dp = atoi(e);
 #define FB(L, DP)                                                                                           \
   hipLaunchKernelGGL((filter_bits_lds_kernel<L, DP>), dim3(grid), dim3(256), (size_t)4 * DP * slot, s, d, \
                      nrows, bits, slot)
-#define FBD(L, DEF) \
-  if ((dp ? dp : DEF) <= 2) FB(L, 2); else if ((dp ? dp : DEF) <= 3) FB(L, 3); else if ((dp ? dp : DEF) <= 4) FB(L, 4); else FB(L, 6);
   switch (ni) {  // the executor keeps ni <= 8
-    case 1: FBD(1, 6); break;
-    case 2: FBD(2, 3); break;
-    case 3: FBD(3, 2); break;
-    case 4: FBD(4, 2); break;
+    case 1: FB(1, 6); break;
+    case 2: FB(2, 3); break;
+    case 3: FB(3, 2); break;
+    case 4: FB(4, 2); break;
     case 5: FB(5, 2); break;
     case 6: FB(6, 2); break;
     case 7: FB(7, 2); break;
     default: FB(8, 2); break;
   }
-#undef FBD
 #undef FB
   CHECK_LAUNCH();
 }
@@ -4032,24 +3680,19 @@ void CompactColumns(const CompactDesc &d, int64_t nrows, const unsigned long lon
   int grid = NumCUs() * gpc;
   const int64_t need = (nrows >> 8) / 4 + 1;
   if (grid > need) grid = (int)need;
-  int dp = 0;  // MBX_CP_DEPTH: ring depth override (sweeps)
-  if (const char *e = Knob("MBX_CP_DEPTH")) dp = atoi(e);
 #define CP(L, DP)                                                                                              \
   hipLaunchKernelGGL((compact_lds_kernel<L, DP>), dim3(grid), dim3(256), (size_t)4 * DP * (L * 1024 + 64) + 4 * 2048, s, d, \
                      nrows, bits, step_offsets)
-#define CPD(L, DEF) \
-  if ((dp ? dp : DEF) <= 2) CP(L, 2); else if ((dp ? dp : DEF) <= 3) CP(L, 3); else if ((dp ? dp : DEF) <= 4) CP(L, 4); else CP(L, 6);
   switch (nld) {
-    case 1: CPD(1, 6); break;
-    case 2: CPD(2, 3); break;
-    case 3: CPD(3, 2); break;
-    case 4: CPD(4, 2); break;
+    case 1: CP(1, 6); break;
+    case 2: CP(2, 3); break;
+    case 3: CP(3, 2); break;
+    case 4: CP(4, 2); break;
     case 5: CP(5, 2); break;
     case 6: CP(6, 2); break;
     case 7: CP(7, 2); break;
     default: CP(8, 2); break;
   }
-#undef CPD
 #undef CP
   CHECK_LAUNCH();
 }

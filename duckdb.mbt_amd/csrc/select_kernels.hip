@@ -1240,19 +1240,10 @@ hipError_t SelectRounds(const SelectDesc &d, const SelectRoundsPlan &p, int64_t 
 // ---------------------------------------------------------------------------
 int64_t CountChunks(int64_t nrows) { return ((nrows >> 8) + FC_CHUNK - 1) / FC_CHUNK; }
 
-// Pass 1 counts every K1 steps (K1 divides FC_CHUNK; MBX_FK_CHUNK, default
-// FC_CHUNK: 1.29 ms at 1e9 INT64 rows vs 1.36 for K1 = 1, which walks the steps
-// grid-stride like the fused filter-aggregate); pass 2 reads the offset of
-// chunk c at entry c * FC_CHUNK / K1 of the scanned counts.
-static int FkChunk() {
-  const char *e = Knob("MBX_FK_CHUNK");
-  const int v = e ? atoi(e) : FC_CHUNK;
-  return (v == 1 || v == 2 || v == 4) ? v : FC_CHUNK;
-}
-int64_t CountEntries(int64_t nrows) {  // pass-1 count entries over the full steps (+1 for the partial step)
-  const int64_t steps = nrows >> 8;
-  return ((steps + FC_CHUNK - 1) / FC_CHUNK) * (FC_CHUNK / FkChunk());
-}
+// Pass 1 writes one count per chunk (1.29 ms at 1e9 INT64 rows vs 1.36 for a
+// count per step, which walks the steps grid-stride like the fused
+// filter-aggregate); pass 2 reads the offset of chunk c at entry c of the
+// scanned counts.
 
 namespace {
 // sequence position p of wave wv -> its step (chunk wv + (p / K) NW, step p % K
@@ -1266,8 +1257,8 @@ __device__ __forceinline__ int64_t cc_step(int64_t p, int64_t wv, int64_t nw, in
 }  // namespace
 
 // pass 1: NI LDS-DMA instructions (KiB of predicate slices) per step, one
-// count per K1 steps
-template <int NI, int DEPTH, int K1>
+// count per chunk
+template <int NI, int DEPTH>
 __global__ __launch_bounds__(256) void filter_count_lds_kernel(FilterMultiDesc D, int64_t n, uint32_t *counts,
                                                                int slot_bytes) {
   extern __shared__ __attribute__((aligned(16))) unsigned char fk_lds[];
@@ -1284,10 +1275,10 @@ __global__ __launch_bounds__(256) void filter_count_lds_kernel(FilterMultiDesc D
     }
   }
   const int64_t nsteps = n >> 8;
-  const int64_t nchunks = ((nsteps + FC_CHUNK - 1) / FC_CHUNK) * (FC_CHUNK / K1);  // count entries
+  const int64_t nchunks = (nsteps + FC_CHUNK - 1) / FC_CHUNK;
   const int64_t nw = (int64_t)gridDim.x * 4, wv = (int64_t)blockIdx.x * 4 + w;
   auto issue = [&](int64_t p, int d) {
-    int64_t q = cc_step<K1>(p, wv, nw, nchunks, nsteps);
+    int64_t q = cc_step<FC_CHUNK>(p, wv, nw, nchunks, nsteps);
     if (q < 0) q = 0;
     unsigned char *dst = ring + d * SB;
 #pragma unroll
@@ -1306,9 +1297,9 @@ __global__ __launch_bounds__(256) void filter_count_lds_kernel(FilterMultiDesc D
     int k = 0;
     uint32_t acc = 0;
     for (int64_t p = 0;; p++) {
-      const int64_t c = wv + (p / K1) * nw;
+      const int64_t c = wv + (p / FC_CHUNK) * nw;
       if (c >= nchunks) break;
-      const int64_t st = c * K1 + p % K1;
+      const int64_t st = c * FC_CHUNK + p % FC_CHUNK;
       asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NI * (DEPTH - 1)) : "memory");
       const unsigned char *src = ring + k * SB;
       bool ok[4] = {st < nsteps, st < nsteps, st < nsteps, st < nsteps};
@@ -1324,7 +1315,7 @@ __global__ __launch_bounds__(256) void filter_count_lds_kernel(FilterMultiDesc D
       issue(p + DEPTH, k);
 #pragma unroll
       for (int e = 0; e < 4; e++) acc += (uint32_t)__popcll(__ballot(ok[e]));
-      if (p % K1 == K1 - 1) {
+      if (p % FC_CHUNK == FC_CHUNK - 1) {
         if (lane == 0) counts[c] = acc;
         acc = 0;
       }
@@ -1361,39 +1352,30 @@ void FilterCountChunks(const FilterMultiDesc &d, int64_t nrows, uint32_t *counts
   const int slot = ni * 1024;
   int gpc = 3;
   if (const char *e = Knob("MBX_FK_BLOCKS_PER_CU")) gpc = atoi(e) > 0 ? atoi(e) : 3;
-  const int64_t chunks = CountEntries(nrows);
+  const int64_t chunks = CountChunks(nrows);
   int64_t grid = (int64_t)NumCUs() * gpc;
   if (grid > chunks / 4 + 1) grid = chunks / 4 + 1;
-  int dp = 0;
-  if (const char *e = Knob("MBX_FK_DEPTH")) dp = atoi(e);
-  const int k1 = FkChunk();
-#define FK1(L, DP, K)                                                                                         \
-  hipLaunchKernelGGL((filter_count_lds_kernel<L, DP, K>), dim3((unsigned)grid), dim3(256), (size_t)4 * DP * slot, s, \
-                     d, nrows, counts, slot)
-#define FK(L, DP) \
-  if (k1 == 8) FK1(L, DP, 8); else if (k1 == 4) FK1(L, DP, 4); else if (k1 == 2) FK1(L, DP, 2); else FK1(L, DP, 1)
-#define FKD(L, DEF) \
-  if ((dp ? dp : DEF) <= 2) FK(L, 2); else if ((dp ? dp : DEF) <= 3) FK(L, 3); else if ((dp ? dp : DEF) <= 4) FK(L, 4); else FK(L, 6);
+#define FK(L, DP)                                                                                                  \
+  hipLaunchKernelGGL((filter_count_lds_kernel<L, DP>), dim3((unsigned)grid), dim3(256), (size_t)4 * DP * slot, s, d, \
+                     nrows, counts, slot)
   switch (ni) {
-    case 1: FKD(1, 6); break;
-    case 2: FKD(2, 6); break;
-    case 3: FKD(3, 3); break;
-    case 4: FKD(4, 3); break;
+    case 1: FK(1, 6); break;
+    case 2: FK(2, 6); break;
+    case 3: FK(3, 3); break;
+    case 4: FK(4, 3); break;
     case 5: FK(5, 2); break;
     case 6: FK(6, 2); break;
     case 7: FK(7, 2); break;
     default: FK(8, 2); break;
   }
-#undef FKD
 #undef FK
-#undef FK1
   (void)hipGetLastError();
 }
 
 // pass 2: NLD KiB of output slices per step; predicates re-evaluated on them
 template <int NLD, int DEPTH>
 __global__ __launch_bounds__(256) void compact_recomp_lds_kernel(CompactDesc D, int64_t n,
-                                                                 const int64_t *__restrict__ offs, int stride) {
+                                                                 const int64_t *__restrict__ offs) {
   extern __shared__ __attribute__((aligned(16))) unsigned char cr_lds[];
   constexpr int SB = NLD * 1024;
   const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -1434,7 +1416,7 @@ __global__ __launch_bounds__(256) void compact_recomp_lds_kernel(CompactDesc D, 
       const int64_t c = wv + (p / FC_CHUNK) * nw;
       if (c >= nchunks) break;
       const int64_t st = c * FC_CHUNK + p % FC_CHUNK;
-      if (p % FC_CHUNK == 0) run = offs[c * stride];
+      if (p % FC_CHUNK == 0) run = offs[c];
       asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NLD * (DEPTH - 1)) : "memory");
       const unsigned char *src = ring + k * SB;
       int64_t v[FC_MAX_OUT][4];
@@ -1511,7 +1493,7 @@ __global__ __launch_bounds__(256) void compact_recomp_lds_kernel(CompactDesc D, 
     unsigned long long bb[4];
 #pragma unroll
     for (int e = 0; e < 4; e++) bb[e] = __ballot(ok[e]);
-    int64_t pos = offs[nchunks * stride] + __popcll(bb[0] & lt) + __popcll(bb[1] & lt) + __popcll(bb[2] & lt) +
+    int64_t pos = offs[nchunks] + __popcll(bb[0] & lt) + __popcll(bb[1] & lt) + __popcll(bb[2] & lt) +
                   __popcll(bb[3] & lt);
     for (int e = 0; e < 4; e++) {
       if (!ok[e]) continue;
@@ -1536,24 +1518,19 @@ void CompactRecompute(const CompactDesc &d, int64_t nrows, const int64_t *chunk_
   const int64_t chunks = CountChunks(nrows);
   int64_t grid = (int64_t)NumCUs() * gpc;
   if (grid > chunks / 4 + 1) grid = chunks / 4 + 1;
-  int dp = 0;
-  if (const char *e = Knob("MBX_CR_DEPTH")) dp = atoi(e);
-#define CR(L, DP)                                                                                               \
-  hipLaunchKernelGGL((compact_recomp_lds_kernel<L, DP>), dim3((unsigned)grid), dim3(256),                      \
-                     (size_t)4 * DP * L * 1024 + 4 * 2048, s, d, nrows, chunk_offsets, FC_CHUNK / FkChunk())
-#define CRD(L, DEF) \
-  if ((dp ? dp : DEF) <= 2) CR(L, 2); else if ((dp ? dp : DEF) <= 3) CR(L, 3); else if ((dp ? dp : DEF) <= 4) CR(L, 4); else CR(L, 6);
+#define CR(L, DP)                                                                          \
+  hipLaunchKernelGGL((compact_recomp_lds_kernel<L, DP>), dim3((unsigned)grid), dim3(256), \
+                     (size_t)4 * DP * L * 1024 + 4 * 2048, s, d, nrows, chunk_offsets)
   switch (nld) {
-    case 1: CRD(1, 6); break;
-    case 2: CRD(2, 3); break;
-    case 3: CRD(3, 2); break;
-    case 4: CRD(4, 2); break;
+    case 1: CR(1, 6); break;
+    case 2: CR(2, 3); break;
+    case 3: CR(3, 2); break;
+    case 4: CR(4, 2); break;
     case 5: CR(5, 2); break;
     case 6: CR(6, 2); break;
     case 7: CR(7, 2); break;
     default: CR(8, 2); break;
   }
-#undef CRD
 #undef CR
   (void)hipGetLastError();
 }

@@ -3,7 +3,7 @@
 table (k, k2 INT32; v, x INT64) once, then for every config of GRID (a JSON
 list of env dicts, read by the library at each launch) times each shape's
 kernels (median of 4 after one warm-up) from the per-query profile.
-Usage: GRID='[{}, {"MBX_FM_DEPTH": 3}]' sweep_env.py rows shape [shape ...]"""
+Usage: GRID='[{}, {"MBX_FM_BLOCKS_PER_CU": 2}]' sweep_env.py rows shape [shape ...]"""
 import json
 import os
 import statistics

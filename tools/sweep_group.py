@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """A/B sweep of the fused GROUP BY (group_direct) launch variants on the C3
 table in ONE process: interleaved rounds, median/min kernel time.  GPU only.
-Variants: MBX_GD_VARIANT = "d<depth>_g<blocks per CU>" (LDS-DMA) or "seg",
+Variants: MBX_GD_VARIANT = "d<2|3>_g<blocks per CU>" (LDS-DMA) or "seg",
 with options "+r<replicas>", "+x1" (XCD-grouped step windows) and "+atomic"
 (the table flush through global atomics instead of per-workgroup records)."""
 import json
@@ -20,7 +20,7 @@ c = m.connect_with_config(cfg).value
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 1_000_000_000
 c.query(f"CREATE TABLE t AS SELECT CAST(mbx_synth(7, i, 32) AS INTEGER) AS k, "
         f"mbx_synth(9, i, 1099511627776) - 549755813888 AS v FROM range({n}) tbl(i)")
-variants = os.environ.get("SWEEP_VARIANTS", "seg,d2_g1,d3_g1,d4_g1,d2_g2,d3_g2").split(",")
+variants = os.environ.get("SWEEP_VARIANTS", "seg,d2_g1,d3_g1,d2_g2,d3_g2").split(",")
 rounds = int(os.environ.get("SWEEP_ROUNDS", "7"))
 sqls = {"c3": "SELECT k, SUM(v), COUNT(*) FROM t GROUP BY k", "count": "SELECT k, COUNT(*) FROM t GROUP BY k"}
 if os.environ.get("SWEEP_SQLS"):

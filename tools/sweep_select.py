@@ -23,18 +23,15 @@ c.query(f"CREATE TABLE t AS SELECT CAST(mbx_synth(7, i, 32) AS INTEGER) AS k, "
 SQLS = {"sel": "SELECT x FROM t WHERE x > 24", "sel2": "SELECT k, v FROM t WHERE x > 24",
         "sel3": "SELECT v FROM t WHERE x > 24 AND k < 16", "sel4": "SELECT x, k FROM t WHERE x > 24 AND k < 16"}
 sqls = {k: SQLS[k] for k in os.environ.get("SWEEP_SQLS", ",".join(SQLS)).split(",")}
-variants = os.environ.get("SWEEP_VARIANTS", "count_first,bits,cf_g2,cf_g4,cf_d2,cf_d4").split(",")
+variants = os.environ.get("SWEEP_VARIANTS", "count_first,bits,cf_g2,cf_g4").split(",")
 rounds = int(os.environ.get("SWEEP_ROUNDS", "5"))
 KN = ("select", "filter_bits", "filter_count", "compact")
 SHAPES = {  # variant -> environment
     "count_first": {}, "bits": {"MBX_CC": "0"}, "one_pass": {"MBX_SL": "1"},
     "cf_g2": {"MBX_CR_BLOCKS_PER_CU": "2", "MBX_FK_BLOCKS_PER_CU": "2"},
     "cf_g4": {"MBX_CR_BLOCKS_PER_CU": "4", "MBX_FK_BLOCKS_PER_CU": "4"},
-    "cf_d2": {"MBX_CR_DEPTH": "2"}, "cf_d4": {"MBX_CR_DEPTH": "4"}, "cf_d6": {"MBX_CR_DEPTH": "6"},
-    "k8": {"MBX_FK_CHUNK": "8"}, "k8_g1": {"MBX_FK_CHUNK": "8", "MBX_FK_BLOCKS_PER_CU": "1"},
     "fk_g1": {"MBX_FK_BLOCKS_PER_CU": "1"}, "fk_g2": {"MBX_FK_BLOCKS_PER_CU": "2"},
-    "fk_g1d4": {"MBX_FK_BLOCKS_PER_CU": "1", "MBX_FK_DEPTH": "4"},
-    "cr_g1": {"MBX_CR_BLOCKS_PER_CU": "1"}, "cr_g1d6": {"MBX_CR_BLOCKS_PER_CU": "1", "MBX_CR_DEPTH": "6"},
+    "cr_g1": {"MBX_CR_BLOCKS_PER_CU": "1"},
 }
 ALLKEYS = sorted({k for v in SHAPES.values() for k in v})
 res = {}
