@@ -429,6 +429,7 @@ static bool JitAggregate(Engine &e, const DRel &src, const BoundSelect &s, DRel 
   try {
     vc.P.pred_reg = 255;
     if (s.where) vc.P.pred_reg = (uint8_t)vc.Compile(*s.where);
+    vc.P.pred_ins = (uint8_t)vc.P.n_ins;
     for (int j = 0; j < na; j++) {
       const AggSpec &a = s.aggs[j];
       if (a.distinct) return false;
@@ -507,6 +508,7 @@ static bool JitGroupAggregate(Engine &e, const DRel &src, const BoundSelect &s, 
   try {
     vc.P.pred_reg = 255;
     if (s.where) vc.P.pred_reg = (uint8_t)vc.Compile(*s.where);
+    vc.P.pred_ins = (uint8_t)vc.P.n_ins;
     for (int i = 0; i < ng; i++) g.key_reg[i] = (uint8_t)vc.Compile(*s.groups[i]);
     for (int j = 0; j < na; j++) {
       const AggSpec &a = s.aggs[j];

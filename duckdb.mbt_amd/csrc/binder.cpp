@@ -172,7 +172,7 @@ static i128 DecimalLimit(int width) { return Pow10(width); }
 static i128 RoundDiv(i128 v, i128 d) {  // round half away from zero
   i128 q = v / d, r = v % d;
   if (r < 0) r = -r;
-  if (2 * r >= d) q += v < 0 ? -1 : 1;
+  if (r >= d - r) q += v < 0 ? -1 : 1;  // 2 * r would overflow at scale 38
   return q;
 }
 
@@ -184,7 +184,23 @@ static bool DoubleToI128(double x, i128 *out) {
   return true;
 }
 
-static double I128ToDouble(i128 v) { return (double)v; }
+// int128 -> double, correctly rounded (one rounding of the 128-bit magnitude);
+// the device uses the same steps (i128_to_double in vm_device.h)
+static double I128ToDouble(i128 v) {
+  bool neg = v < 0;
+  u128 m = neg ? (u128)0 - (u128)v : (u128)v;
+  uint64_t hi = (uint64_t)(m >> 64), lo = (uint64_t)m;
+  double d;
+  if (hi == 0) {
+    d = (double)lo;
+  } else {
+    int sh = __builtin_clzll(hi);
+    uint64_t top = sh ? (hi << sh) | (lo >> (64 - sh)) : hi;
+    if (lo << sh) top |= 1;  // sticky bit: the discarded low bits only matter as "non-zero"
+    d = std::ldexp((double)top, 64 - sh);
+  }
+  return neg ? -d : d;
+}
 
 Value CastValue(const Value &v, const LogicalType &to, bool try_cast) {
   Value out;
@@ -361,12 +377,11 @@ Value CastValue(const Value &v, const LogicalType &to, bool try_cast) {
       return out;
     }
     if (to.id == T_DOUBLE || to.id == T_FLOAT) {
+      // decimal -> double is double(raw) / 10^scale, two correctly rounded
+      // steps: the rule of the device VM (V_DEC2F_*), so a constant and a
+      // column form of one expression return the same bits (VM)
       double d = I128ToDouble(x);
       if (fscale) d = d / (double)Pow10(fscale);
-      if (fscale) {
-        // exact decimal -> double (round-trip via string like DuckDB's cast)
-        d = strtod(FormatDecimal(x, fscale).c_str(), nullptr);
-      }
       out.d = to.id == T_FLOAT ? (double)(float)d : d;
       return out;
     }
@@ -632,14 +647,18 @@ Value EvalConst(const BExpr &e) {
     case B_IDIV:
     case B_DIV:
       if (y == 0) return Value::Null(t);
-      r = x / y;
+      if (y == -1) ovf = __builtin_sub_overflow((i128)0, x, &r);  // MIN / -1 has no int128 quotient
+      else r = x / y;
       break;
     case B_MOD:
       if (y == 0) return Value::Null(t);
-      r = x % y;
+      r = y == -1 ? 0 : x % y;
       break;
     case B_NEG: ovf = __builtin_sub_overflow((i128)0, x, &r); break;
-    case B_ABS: r = x < 0 ? -x : x; break;
+    case B_ABS:
+      if (x < 0) ovf = __builtin_sub_overflow((i128)0, x, &r);
+      else r = x;
+      break;
     default: ThrowError("Internal", "bad integer op");
   }
   r = CheckedIntResult(e.op, t, r, x, y, ovf);

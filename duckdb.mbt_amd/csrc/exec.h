@@ -227,6 +227,10 @@ struct ProfScope {
     e.events.push_back(pe);
     idx = e.events.size() - 1;
   }
+  // the event's name, once the scope knows which kernel it launched
+  void Rename(const char *name) {
+    if (on) e.events[idx].name = name;
+  }
   ~ProfScope() {
     if (on) hipEventRecord(e.events[idx].b, e.stream);
   }

@@ -354,8 +354,10 @@ DRel FilterProject(Engine &e, const DRel &rel, const BExprPtr &pred, const std::
       offs = Alloc(e, std::max<int64_t>(ntiles, 1) * 8);
       {
         ProfScope ps(e, "vm_filter", 0, n);
-        if (!jit::VmFilter(vc.P, vc.cols, n, rel.rs, rel.rstep, (uint64_t *)bits->p, (uint32_t *)counts->p, e.d_err,
-                           e.stream))
+        if (jit::VmFilter(vc.P, vc.cols, n, rel.rs, rel.rstep, (uint64_t *)bits->p, (uint32_t *)counts->p, e.d_err,
+                          e.stream))
+          ps.Rename("jit_filter");  // the specialised kernel ran, not the interpreter
+        else
           dev::VmFilter(vc.P, vc.cols, n, rel.rs, rel.rstep, (uint64_t *)bits->p, (uint32_t *)counts->p, e.d_err,
                         e.stream);
       }
@@ -404,8 +406,10 @@ DRel FilterProject(Engine &e, const DRel &rel, const BExprPtr &pred, const std::
     }
     if (nsel > 0) {
       ProfScope ps(e, "vm_project", 0, n);
-      if (!jit::VmProject(vc.P, vc.cols, n, rel.rs, rel.rstep, bits ? (const uint64_t *)bits->p : nullptr,
+      if (jit::VmProject(vc.P, vc.cols, n, rel.rs, rel.rstep, bits ? (const uint64_t *)bits->p : nullptr,
                      offs ? (const int64_t *)offs->p : nullptr, vo, e.d_err, e.stream))
+        ps.Rename("jit_project");
+      else
         dev::VmProject(vc.P, vc.cols, n, rel.rs, rel.rstep, bits ? (const uint64_t *)bits->p : nullptr,
                      offs ? (const int64_t *)offs->p : nullptr, vo, e.d_err, e.stream);
     }

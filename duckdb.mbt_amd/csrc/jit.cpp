@@ -74,9 +74,9 @@ std::string Preload(const VmProgram &p, const std::string &sfx, const std::strin
   return o.str();
 }
 
-std::string Body(const VmProgram &p, const std::string &sfx = "") {
+std::string Body(const VmProgram &p, const std::string &sfx = "", int from = 0, int to = -1) {
   std::ostringstream o;
-  for (int k = 0; k < p.n_ins; k++) {
+  for (int k = from; k < (to < 0 ? p.n_ins : to); k++) {
     const VmIns &I = p.ins[k];
     if (I.op == V_LOADCOL) {
       o << "      R.lo(" << (int)I.dst << ") = L" << k << "l" << sfx << "; R.hi(" << (int)I.dst << ") = L" << k << "h" << sfx
@@ -86,6 +86,18 @@ std::string Body(const VmProgram &p, const std::string &sfx = "") {
     o << "      vm_step<LocalRF, true>(P, Cs, " << (int)I.op << ", " << (int)I.dst << ", " << (int)I.a << ", "
       << (int)I.b << ", " << (int)I.c << ", " << (int)I.aux << ", lrow, active, rs, rstep, R, err);\n";
   }
+  return o.str();
+}
+
+// Body of a fused aggregate program: the predicate's instructions, then the
+// aggregate arguments with `active` narrowed to the rows the predicate keeps
+// (a row the WHERE clause rejects must not raise).
+std::string FusedBody(const VmProgram &p, const std::string &sfx) {
+  if (p.pred_reg == 255) return Body(p, sfx);
+  std::ostringstream o;
+  o << Body(p, sfx, 0, p.pred_ins) << "      active = active && !R.nl(" << (int)p.pred_reg << ") && R.lo(" << (int)p.pred_reg
+    << ") != 0;\n"
+    << Body(p, sfx, p.pred_ins);
   return o.str();
 }
 
@@ -134,8 +146,10 @@ std::string CompileToCode(const std::string &src, std::vector<char> *code) {
   hiprtcProgram prog;
   if (hiprtcCreateProgram(&prog, src.c_str(), "mbx_jit.hip", 0, nullptr, nullptr) != HIPRTC_SUCCESS)
     return "hiprtcCreateProgram failed";
-  const char *opts[] = {"--offload-arch=gfx950", "-O3", "-std=c++17"};
-  hiprtcResult r = hiprtcCompileProgram(prog, 3, opts);
+  // no contraction: a * b + c rounds the product first, as the tile interpreter
+  // does (its registers are LDS planes), so both engines return the same bits
+  const char *opts[] = {"--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off"};
+  hiprtcResult r = hiprtcCompileProgram(prog, 4, opts);
   std::string log;
   size_t ls = 0;
   if (hiprtcGetProgramLogSize(prog, &ls) == HIPRTC_SUCCESS && ls > 1) {
@@ -373,9 +387,9 @@ static std::string AggSource(const VmProgram &p, const dev::VmCols &cols) {
       o << Preload(p, std::to_string(r), "lrow" + std::to_string(r), "act" + std::to_string(r));
   }
   for (int r = 0; r < NR; r++) {
-    o << "    {\n      const int64_t lrow = lrow" << r << ";\n      const bool active = act" << r
+    o << "    {\n      const int64_t lrow = lrow" << r << ";\n      bool active = act" << r
       << ";\n      LocalRF &R = R" << r << ";\n";
-    o << Body(p, std::to_string(r));
+    o << FusedBody(p, std::to_string(r));
     o << "    }\n";
   }
   o << "#pragma unroll\n    for (int u = 0; u < " << NR << "; u++) {\n      LocalRF &R = ";
@@ -577,9 +591,9 @@ static std::string GroupSource(const VmProgram &p, const dev::VmCols &cols, cons
       << " = {};\n";
   for (int r = 0; r < U; r++) o << Preload(p, std::to_string(r), "lrow" + std::to_string(r), "act" + std::to_string(r));
   for (int r = 0; r < U; r++) {
-    o << "    {\n      const int64_t lrow = lrow" << r << ";\n      const bool active = act" << r
+    o << "    {\n      const int64_t lrow = lrow" << r << ";\n      bool active = act" << r
       << ";\n      LocalRF &R = R" << r << ";\n";
-    o << Body(p, std::to_string(r));
+    o << FusedBody(p, std::to_string(r));
     o << "    }\n";
   }
   for (int r = 0; r < U; r++) {

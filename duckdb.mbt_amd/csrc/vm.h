@@ -35,13 +35,12 @@ enum VmOpc : uint8_t {
   V_DISTINCT_I, V_DISTINCT_L, V_DISTINCT_F,  // aux=1 -> NOT DISTINCT
   // conversions
   V_I2L,          // sign-extend 64 -> 128
-  V_U2L,          // zero-extend 64 -> 128 (UBIGINT storage)
   V_L2I,          // 128 -> 64 (range check; b/c = const ids of lo/hi bound, 255 = int64 range)
   V_I2F, V_L2F,   // -> double
   V_F2I, V_F2L,   // double -> integer (round to nearest even, range check via b/c)
-  V_CHECK_I,      // range check r[a] within [const[b], const[c]] (64 bit), then copy
+  V_CHECK_I,      // range check r[a] within [const[b], const[c]] (64 bit), then copy; aux = VmErr to raise
   V_CHECK_L,      // same for 128-bit registers
-  V_SCALEUP_I, V_SCALEUP_L,  // r = r * 10^aux (overflow -> error)
+  V_SCALEUP_I, V_SCALEUP_L,  // r = r * 10^aux (overflow -> E_CAST_RANGE: only casts rescale)
   V_SCALEDN_I, V_SCALEDN_L,  // r = round_half_away(r / 10^aux)
   V_DEC2F_I, V_DEC2F_L,      // double(r) / 10^aux
   V_F2DEC_I, V_F2DEC_L,      // round(r * 10^aux) with range check const[b], const[c]
@@ -78,7 +77,10 @@ struct VmProgram {
   uint8_t out_phys[VM_MAX_OUT];   // store format of each output
   uint8_t out_class[VM_MAX_OUT];
   uint8_t pred_reg;               // predicate register (filter programs)
-  uint8_t pad[3];
+  // fused aggregate programs: the first pred_ins instructions compute the
+  // predicate; the rest (the aggregate arguments) may raise only for rows it keeps
+  uint8_t pred_ins;
+  uint8_t pad[2];
 };
 
 // Error codes written by kernels to the device error word.

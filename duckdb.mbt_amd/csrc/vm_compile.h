@@ -114,13 +114,25 @@ struct VmCompiler {
     ThrowError("Not implemented", "unsupported register class conversion on device");
   }
 
-  int RangeCheck(int r, VClass vc, i128 lo, i128 hi) {
-    return Step1(vc == VC_I128 ? V_CHECK_L : V_CHECK_I, r, Const(lo), Const(hi));
+  // errcode: what a value outside [lo, hi] raises (a cast: E_CAST_RANGE; the
+  // result of an arithmetic step: that step's overflow code, as the host folder)
+  int RangeCheck(int r, VClass vc, i128 lo, i128 hi, int errcode = E_CAST_RANGE) {
+    return Step1(vc == VC_I128 ? V_CHECK_L : V_CHECK_I, r, Const(lo), Const(hi), errcode);
+  }
+  // Result check of integer arithmetic in a type narrower than its register
+  // class: TINYINT..INTEGER and the unsigned types in 64 bits, UBIGINT in 128.
+  int CheckArith(int d, VClass vc, const LogicalType &t, int errcode) {
+    bool narrow = vc == VC_I64 ? (IsIntegral(t.id) && t.id != T_BIGINT) : (vc == VC_I128 && t.id == T_UBIGINT);
+    if (!narrow) return d;
+    i128 lo, hi;
+    IntegralRange(t.id, &lo, &hi);
+    return RangeCheck(d, vc, lo, hi, errcode);
   }
 
+  // rounds to FLOAT: x * 1.0 keeps the sign of a zero (x + 0.0 would not)
   int ToFloat32(int r) {
-    int z = LoadConst(ConstF(0.0));
-    return Step2(V_ADD_F, r, z, 1);
+    int z = LoadConst(ConstF(1.0));
+    return Step2(V_MUL_F, r, z, 1);
   }
 
   int CompileCast(const BExpr &e) {
@@ -159,11 +171,15 @@ struct VmCompiler {
     }
     if ((fint || fdec) && tdec) {
       int fs = fdec ? from.scale : 0;
-      int x = ToClass(r, fc, tc);
+      // rescale in the wider of the two classes: a 128-bit value may fit the
+      // 64-bit target only after it has been scaled down
+      VClass wc = fc == VC_I128 ? fc : tc;
+      int x = ToClass(r, fc, wc);
       int ds = to.scale - fs;
-      if (ds > 0) x = Step1(tc == VC_I128 ? V_SCALEUP_L : V_SCALEUP_I, x, 0, 0, ds);
-      else if (ds < 0) x = Step1(tc == VC_I128 ? V_SCALEDN_L : V_SCALEDN_I, x, 0, 0, -ds);
+      if (ds > 0) x = Step1(wc == VC_I128 ? V_SCALEUP_L : V_SCALEUP_I, x, 0, 0, ds);
+      else if (ds < 0) x = Step1(wc == VC_I128 ? V_SCALEDN_L : V_SCALEDN_I, x, 0, 0, -ds);
       i128 lim = Pow10(to.width) - 1;
+      if (wc != tc) return Step1(V_L2I, x, Const(-lim), Const(lim));
       return RangeCheck(x, tc, -lim, lim);
     }
     if (fdec && tint) {
@@ -286,13 +302,7 @@ struct VmCompiler {
         int a = Compile(*e.ch[0]);
         uint8_t op = e.op == B_NEG ? (vc == VC_F64 ? V_NEG_F : vc == VC_I128 ? V_NEG_L : V_NEG_I)
                                    : (vc == VC_F64 ? V_ABS_F : vc == VC_I128 ? V_ABS_L : V_ABS_I);
-        int d = Step1(op, a);
-        if (vc == VC_I64 && IsIntegral(t.id) && t.id != T_BIGINT) {
-          i128 lo, hi;
-          IntegralRange(t.id, &lo, &hi);
-          return RangeCheck(d, vc, lo, hi);
-        }
-        return d;
+        return CheckArith(Step1(op, a), vc, t, E_OVF_NEG);
       }
       case B_ADD: case B_SUB: case B_MUL: case B_DIV: case B_IDIV: case B_MOD: {
         if (t.id == T_DATE || t.id == T_TIMESTAMP || t.id == T_INTERVAL)
@@ -312,13 +322,8 @@ struct VmCompiler {
                                 : e.op == B_MOD ? V_MOD_L : V_DIV_L;
         else op = e.op == B_ADD ? V_ADD_I : e.op == B_SUB ? V_SUB_I : e.op == B_MUL ? V_MUL_I
                   : e.op == B_MOD ? V_MOD_I : V_DIV_I;
-        int d = Step2(op, a, b);
-        if (vc == VC_I64 && IsIntegral(t.id) && t.id != T_BIGINT) {
-          i128 lo, hi;
-          IntegralRange(t.id, &lo, &hi);
-          return RangeCheck(d, vc, lo, hi);
-        }
-        return d;
+        return CheckArith(Step2(op, a, b), vc, t,
+                          e.op == B_ADD ? E_OVF_ADD : e.op == B_SUB ? E_OVF_SUB : e.op == B_MUL ? E_OVF_MUL : E_OVF_NEG);
       }
       default:
         ThrowError("Not implemented", "function " + ExprToString(e) + " is not supported on the MI355X device path");

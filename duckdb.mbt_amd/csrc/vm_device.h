@@ -131,12 +131,17 @@ __device__ __forceinline__ int64_t pow10_64(int k) {
   return r;
 }
 
-// int128 -> double through the magnitude (no cancellation between the
-// halves); exact rounding whenever |v| < 2^64.
+// int128 -> double through the magnitude, correctly rounded: the top 64
+// significant bits with a sticky bit for the rest are rounded once, and the
+// power-of-two scaling is exact.  The host folder does the same steps
+// (I128ToDouble in binder.cpp).
 __device__ __forceinline__ double u128_to_double(u128 m) {
   uint64_t hi = (uint64_t)(m >> 64), lo = (uint64_t)m;
   if (hi == 0) return (double)lo;
-  return (double)hi * 18446744073709551616.0 + (double)lo;
+  int sh = __clzll((long long)hi);
+  uint64_t top = sh ? (hi << sh) | (lo >> (64 - sh)) : hi;
+  if (lo << sh) top |= 1;
+  return ldexp((double)top, 64 - sh);
 }
 __device__ __forceinline__ double i128_to_double(i128 v) {
   if (v < 0) return -u128_to_double((u128)0 - (u128)v);
@@ -260,7 +265,7 @@ __device__ __forceinline__ void vm_step(const VmProgram &P, const VmCols &C, int
       default: {
         // null-propagating unary/binary ops
         nl = R.nl(a);
-        if (op >= V_ADD_I && op != V_NOT && op != V_I2L && op != V_U2L && op != V_L2I && op != V_I2F &&
+        if (op >= V_ADD_I && op != V_NOT && op != V_I2L && op != V_L2I && op != V_I2F &&
             op != V_L2F && op != V_F2I && op != V_F2L && op != V_CHECK_I && op != V_CHECK_L &&
             op != V_SCALEUP_I && op != V_SCALEUP_L && op != V_SCALEDN_I && op != V_SCALEDN_L &&
             op != V_DEC2F_I && op != V_DEC2F_L && op != V_F2DEC_I && op != V_F2DEC_L &&
@@ -299,6 +304,12 @@ __device__ __forceinline__ void vm_step(const VmProgram &P, const VmCols &C, int
           case V_DIV_L: case V_MOD_L: {
             i128 x = mk128(xa, xah), y = mk128(xb, xbh);
             if (y == 0) { nl = 1; break; }
+            if (y == -1) {  // MIN / -1 has no 128-bit quotient; x % -1 is 0
+              i128 r = 0;
+              if (op == V_DIV_L && sub_ovf128((i128)0, x, r) && ok) raise_err(err, E_OVF_MUL);
+              sp128(r, lo, hi);
+              break;
+            }
             i128 r = op == V_DIV_L ? sdiv128(x, y) : smod128(x, y);
             sp128(r, lo, hi);
             break;
@@ -310,8 +321,9 @@ __device__ __forceinline__ void vm_step(const VmProgram &P, const VmCols &C, int
             break;
           }
           case V_ABS_L: {
-            i128 x = mk128(xa, xah);
-            sp128(x < 0 ? -x : x, lo, hi);
+            i128 x = mk128(xa, xah), r = x;
+            if (x < 0 && sub_ovf128((i128)0, x, r) && ok) raise_err(err, E_OVF_NEG);
+            sp128(r, lo, hi);
             break;
           }
           case V_ADD_F: case V_SUB_F: case V_MUL_F: case V_DIV_F: case V_MOD_F: case V_IDIV_F: {
@@ -347,7 +359,6 @@ __device__ __forceinline__ void vm_step(const VmProgram &P, const VmCols &C, int
           case V_TOBOOL_I: lo = (xa != 0 || xah != 0); break;
           case V_TOBOOL_F: lo = __longlong_as_double(xa) != 0.0; break;
           case V_I2L: lo = xa; hi = xa >> 63; break;
-          case V_U2L: lo = xa; hi = 0; break;
           case V_L2I: {
             i128 x = mk128(xa, xah);
             i128 mn = b == 255 ? (i128)INT64_MIN : mk128(P.consts[b].lo, P.consts[b].hi);
@@ -357,14 +368,14 @@ __device__ __forceinline__ void vm_step(const VmProgram &P, const VmCols &C, int
             break;
           }
           case V_CHECK_I: {
-            if ((xa < P.consts[b].lo || xa > P.consts[c].lo) && ok) raise_err(err, E_CAST_RANGE);
+            if ((xa < P.consts[b].lo || xa > P.consts[c].lo) && ok) raise_err(err, aux);
             lo = xa;
             break;
           }
           case V_CHECK_L: {
             i128 x = mk128(xa, xah);
             if ((x < mk128(P.consts[b].lo, P.consts[b].hi) || x > mk128(P.consts[c].lo, P.consts[c].hi)) && ok)
-              raise_err(err, E_CAST_RANGE);
+              raise_err(err, aux);
             lo = xa;
             hi = xah;
             break;
@@ -380,10 +391,10 @@ __device__ __forceinline__ void vm_step(const VmProgram &P, const VmCols &C, int
             sp128(v, lo, hi);
             break;
           }
-          case V_SCALEUP_I: if (__builtin_mul_overflow(xa, pow10_64(aux), &lo) && ok) raise_err(err, E_DEC_OVF); break;
+          case V_SCALEUP_I: if (__builtin_mul_overflow(xa, pow10_64(aux), &lo) && ok) raise_err(err, E_CAST_RANGE); break;
           case V_SCALEUP_L: {
             i128 r;
-            if (mul_ovf128(mk128(xa, xah), pow10_128(aux), r) && ok) raise_err(err, E_DEC_OVF);
+            if (mul_ovf128(mk128(xa, xah), pow10_128(aux), r) && ok) raise_err(err, E_CAST_RANGE);
             sp128(r, lo, hi);
             break;
           }
@@ -398,14 +409,18 @@ __device__ __forceinline__ void vm_step(const VmProgram &P, const VmCols &C, int
             i128 x = mk128(xa, xah), p = pow10_128(aux);
             i128 q = sdiv128(x, p), r = x - q * p;
             i128 ar = r < 0 ? -r : r;
-            if (2 * ar >= p) q += x < 0 ? -1 : 1;
+            if (ar >= p - ar) q += x < 0 ? -1 : 1;  // 2 * ar would overflow at 10^38
             sp128(q, lo, hi);
             break;
           }
+          // decimal -> double is double(raw) / double(10^scale): two correctly
+          // rounded steps, the same two as the host folder (CastValue)
           case V_DEC2F_I: lo = __double_as_longlong((double)xa / (double)pow10_64(aux)); break;
-          case V_DEC2F_L: lo = __double_as_longlong(i128_to_double(mk128(xa, xah)) / (double)pow10_128(aux)); break;
+          case V_DEC2F_L:
+            lo = __double_as_longlong(i128_to_double(mk128(xa, xah)) / i128_to_double(pow10_128(aux)));
+            break;
           case V_F2DEC_I: case V_F2DEC_L: {
-            double x = rint(__longlong_as_double(xa) * (double)pow10_128(aux));
+            double x = rint(__longlong_as_double(xa) * i128_to_double(pow10_128(aux)));
             bool bad = !(x >= -1.7014118346046923e38 && x < 1.7014118346046923e38);
             i128 v = bad ? 0 : (i128)x;
             i128 mn = mk128(P.consts[b].lo, P.consts[b].hi), mx = mk128(P.consts[c].lo, P.consts[c].hi);

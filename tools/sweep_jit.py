@@ -2,7 +2,8 @@
 """A/B of run-time compiled kernel shapes in ONE process (interleaved rounds).
 GPU only.  Environment:
   SWEEP_SQL       the query (default: the fused aggregate shape)
-  SWEEP_KERNEL    profiled kernel name to time (default jit_aggregate)
+  SWEEP_KERNEL    profiled kernel name to time (default jit_aggregate; jit_group,
+                  jit_filter and jit_project are the other compiled shapes)
   SWEEP_VARIANTS  variants separated by ',', each a ':'-separated list of
                   NAME=value settings (e.g. MBX_JIT_U=4:MBX_JIT_BPC=4)
 Usage: sweep_jit.py [rows]"""
