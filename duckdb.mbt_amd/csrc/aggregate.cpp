@@ -103,6 +103,23 @@ static DRel KeyedEmit(Engine &e, const BoundSelect &s, const LogicalType &key_ty
   return out;
 }
 
+// The shape of a direct GROUP BY for group_direct_plan.h (the predicates are
+// the caller's to add)
+static GroupDirectShape DirectShape(int64_t n, int nk, Phys kphys, Phys vphys, int nv, bool mm, int vm, i128 maxabs) {
+  GroupDirectShape sh;
+  sh.n = n;
+  sh.nk = nk;
+  sh.key_bytes = PhysSize(kphys);
+  sh.val_bytes = PhysSize(vphys);
+  sh.nv = nv;
+  sh.mm = mm;
+  sh.vm = vm;
+  sh.maxabs = (unsigned __int128)maxabs;
+  sh.num_cus = dev::NumCUs();
+  sh.knobs = dev::GroupDirectKnobsFromEnv();
+  return sh;
+}
+
 // LDS direct-index reduction (group_direct kernels): rows with an integer key
 // in [kmin, kmin + nk) (no NULL keys) and <= 2 integer value columns of one
 // physical type without NULLs.  Fills cs (COUNT(*) per key) and s0/s1 (one
@@ -118,35 +135,28 @@ static bool DirectReduce(Engine &e, const void *kdata, Phys kphys, int64_t kmin,
   if (kphys != P_I32 && kphys != P_I64) return false;
   for (auto *v : vals)
     if ((v->phys != P_I32 && v->phys != P_I64) || v->validity || v->phys != vals[0]->phys) return false;
-  int R = 64;
-  while (R > 1 && dev::GroupDirectLds((int)nk, R, nv, mm) > 48 * 1024) R >>= 1;
-  if (dev::GroupDirectLds((int)nk, R, nv, mm) > 64 * 1024) return false;
-  int64_t seg = 0;  // whole chunk
-  if (maxabs > 0) {
-    i128 per_rep = ((i128)1 << 62) / maxabs;  // rows one replica may absorb
-    i128 seg128 = per_rep * R;
-    if (seg128 < 4096) return false;
-    if (seg128 < (i128)INT64_MAX / 2) seg = (int64_t)seg128;
-  }
-  if ((int64_t)R * ((int64_t)1 << 31) < seg || seg == 0) {
-    // u32 replica counts: cap segment length
-    int64_t cap = (int64_t)R * ((int64_t)1 << 30);
-    if (seg == 0 || seg > cap) seg = cap;
-  }
+  dev::GroupDirectArgs a{};
+  a.shape = DirectShape(n, (int)nk, kphys, nv ? vals[0]->phys : P_I64, nv, mm, 0, maxabs);
+  const GroupDirectPlan plan = PlanGroupDirect(a.shape);
+  // (no NULLs and no predicates: one of the two kernels always takes a shape that fits)
+  if (plan.form != GroupDirectForm::LdsOneFlush && plan.form != GroupDirectForm::Segmented) return false;
   size_t st_bytes = (size_t)nk * sizeof(dev::AggState);
   out.cs = Alloc(e, nk * 8, true);
   out.s0 = Alloc(e, st_bytes);
   out.s1 = Alloc(e, st_bytes);
   dev::InitAggStates((dev::AggState *)out.s0->p, nk, e.stream);
   dev::InitAggStates((dev::AggState *)out.s1->p, nk, e.stream);
-  const Phys vphys = nv ? vals[0]->phys : P_I64;
   double bytes = (double)n * PhysSize(kphys);
   for (auto *v : vals) bytes += (double)n * PhysSize(v->phys);
   ProfScope ps(e, "group_direct", bytes, n);
-  dev::GroupByDirectStates(kdata, kphys, kmin, (int)nk, nv > 0 ? vals[0]->data : nullptr,
-                           nv > 1 ? vals[1]->data : nullptr, vphys, nv, mm, n, seg, R,
-                           (unsigned long long *)out.cs->p, (dev::AggState *)out.s0->p, (dev::AggState *)out.s1->p, 0,
-                           e.stream, nullptr, maxabs < ((i128)1 << 62) ? (uint64_t)maxabs : ~0ull);
+  a.keys = kdata;
+  a.v0 = nv > 0 ? vals[0]->data : nullptr;
+  a.v1 = nv > 1 ? vals[1]->data : nullptr;
+  a.kmin = kmin;
+  a.cstar = (unsigned long long *)out.cs->p;
+  a.st0 = (dev::AggState *)out.s0->p;
+  a.st1 = (dev::AggState *)out.s1->p;
+  dev::GroupDirectLaunch(a, plan, e.stream);
   return true;
 }
 
@@ -1084,71 +1094,56 @@ static bool DirectGroupAggregate(Engine &e, const DRel &src, const BoundSelect &
   if (!ok) return false;
   int nk = (int)range + (knull ? 1 : 0);  // + the NULL group's slot, last
   int nv = (int)vcols.size();
-  int R = 64;
-  while (R > 1 && dev::GroupDirectLds(nk, R, nv, mm, vm) > 48 * 1024) R >>= 1;
-  if (dev::GroupDirectLds(nk, R, nv, mm, vm) > 64 * 1024) ok = false;
-  int64_t seg = 0;  // whole chunk
-  if (maxabs > 0) {
-    i128 per_rep = ((i128)1 << 62) / maxabs;  // rows one replica may absorb
-    i128 seg128 = per_rep * R;
-    if (seg128 < 4096) ok = false;
-    if (seg128 < (i128)INT64_MAX / 2) seg = (int64_t)seg128;
-  }
-  if ((int64_t)R * ((int64_t)1 << 31) < seg || seg == 0) {
-    // u32 replica counts: cap segment length
-    int64_t cap = (int64_t)R * ((int64_t)1 << 30);
-    if (seg == 0 || seg > cap) seg = cap;
-  }
-  if (!ok) return false;
-  int64_t nslots = nk;
-  size_t st_bytes = (size_t)nslots * sizeof(dev::AggState);
-  // both value columns' states in one block, zeroed with the COUNT(*) slots
-  // by one launch ahead of the scan
-  auto cs = Alloc(e, nslots * 8);
-  auto sb = Alloc(e, 2 * st_bytes);
-  dev::AggState *const s0p = (dev::AggState *)sb->p, *const s1p = s0p + nslots;
-  // GroupByDirectStates initialises the states for its atomic forms, or
-  // has every workgroup write a record of its table (up to
-  // kGroupPartialKeys keys) that GroupPartialsCompact reduces
-  DevBufPtr gparts;
-  dev::GroupPartialsOut po;
-  memset(&po, 0, sizeof(po));
-  po.state_slots = 2 * nslots;
-  if (nk <= dev::kGroupPartialKeys) {
-    po.bytes = (size_t)nk * dev::NumCUs() * 3 * dev::GroupPartialWords(2, true) * 8;
-    gparts = Alloc(e, po.bytes);
-    po.buf = gparts->p;
-  }
-  Phys vphys = nv ? src.cols[vcols[0]].phys : P_I64;
+  dev::GroupDirectArgs a{};
+  a.shape = DirectShape(src.n, nk, K.phys, nv ? src.cols[vcols[0]].phys : P_I64, nv, mm, vm, maxabs);
+  a.shape.records_offered = true;
   double bytes = (double)src.n * PhysSize(K.phys);
   for (int c : vcols) bytes += (double)src.n * PhysSize(src.cols[c].phys);
   bytes += __builtin_popcount(vm) * (src.n / 8.0);  // validity words
-  dev::GroupPreds gp;
-  memset(&gp, 0, sizeof(gp));
   for (auto &kv : f2_ranges) {
     const int kcol = s.groups[0]->col, pc = kv.first;
-    dev::GroupPred &g = gp.p[gp.n++];
+    dev::GroupPred &g = a.preds.p[a.preds.n++];
     g.src = pc == kcol ? 2 : (nv > 0 && pc == vcols[0]) ? 3 : 1;
     g.phys = src.cols[pc].phys;
     g.col = src.cols[pc].data;
     g.lo = (int64_t)std::max<i128>(kv.second.first, INT64_MIN);
     g.span = (uint64_t)((int64_t)std::min<i128>(kv.second.second, INT64_MAX)) - (uint64_t)g.lo;
-    if (g.src == 1) bytes += (double)src.n * PhysSize(src.cols[pc].phys);
+    if (g.src == 1) {
+      bytes += (double)src.n * PhysSize(src.cols[pc].phys);
+      a.shape.pred_bytes[a.shape.npred_own++] = PhysSize(src.cols[pc].phys);
+    }
   }
-  bool launched;
-  {
+  a.shape.npred = a.preds.n;
+  const GroupDirectPlan plan = PlanGroupDirect(a.shape);
+  if (plan.form == GroupDirectForm::Unfit) return false;
+  if (plan.form == GroupDirectForm::Refused) {
+    // (the profile keeps the group_direct entry a refused launch has always left)
     ProfScope ps(e, "group_direct", bytes, src.n);
-    launched = dev::GroupByDirectStates(K.data, K.phys, (int64_t)ks->imin, nk,
-                                        nv > 0 ? src.cols[vcols[0]].data : nullptr,
-                                        nv > 1 ? src.cols[vcols[1]].data : nullptr, vphys, nv, mm, src.n, seg,
-                                        R, (unsigned long long *)cs->p, s0p,
-                                        s1p, 0, e.stream, gp.n ? &gp : nullptr,
-                                        maxabs < ((i128)1 << 62) ? (uint64_t)maxabs : ~0ull,
-                                        vm ? &gval : nullptr, &po);
-  }
-  if (!launched) {
     *refused = true;
     return false;
+  }
+  int64_t nslots = nk;
+  size_t st_bytes = (size_t)nslots * sizeof(dev::AggState);
+  // both value columns' states in one block; the launch zeroes them with the
+  // COUNT(*) slots for its atomic forms, or has every workgroup write a record
+  // of its table that GroupPartialsCompact reduces
+  auto cs = Alloc(e, nslots * 8);
+  auto sb = Alloc(e, 2 * st_bytes);
+  dev::AggState *const s0p = (dev::AggState *)sb->p, *const s1p = s0p + nslots;
+  DevBufPtr gparts = plan.records ? Alloc(e, plan.record_bytes) : nullptr;
+  a.keys = K.data;
+  a.v0 = nv > 0 ? src.cols[vcols[0]].data : nullptr;
+  a.v1 = nv > 1 ? src.cols[vcols[1]].data : nullptr;
+  a.kmin = (int64_t)ks->imin;
+  a.valid = gval;
+  a.cstar = (unsigned long long *)cs->p;
+  a.st0 = s0p;
+  a.st1 = s1p;
+  a.init_state_slots = 2 * nslots;
+  a.records = plan.records ? gparts->p : nullptr;
+  {
+    ProfScope ps(e, "group_direct", bytes, src.n);
+    dev::GroupDirectLaunch(a, plan, e.stream);
   }
   auto list = Alloc(e, nslots * 4);
   // the group count: left on the device for ToHost when this is the
@@ -1156,7 +1151,7 @@ static bool DirectGroupAggregate(Engine &e, const DRel &src, const BoundSelect &
   const bool defer = CountMayStayOnDevice(e, s);
   DevBufPtr nbuf = defer ? Alloc(e, 8) : nullptr;
   int64_t *const n_out = defer ? (int64_t *)nbuf->p : e.d_scratch;
-  if (!po.used)
+  if (!plan.records)
     dev::CompactSlots((const unsigned long long *)cs->p, nslots, (int32_t *)list->p, n_out, e.stream);
   // outputs sized for every slot (<= 1024 rows), unlike the generic paths'
   // (sized for the groups): the emit reads the group count from the device, so
@@ -1171,9 +1166,9 @@ static bool DirectGroupAggregate(Engine &e, const DRel &src, const BoundSelect &
         return EmitIn{stp, VC_I64};
       },
       D);
-  if (po.used)  // records reduced, keys compacted and the relation written by one launch
-    dev::GroupPartialsCompact(po, nv, mm, nk, (unsigned long long *)cs->p, s0p, s1p, (int32_t *)list->p,
-                              n_out, e.stream, &D);
+  if (plan.records)  // records reduced, keys compacted and the relation written by one launch
+    dev::GroupPartialsCompact(gparts->p, plan.grid, nv, mm, nk, (unsigned long long *)cs->p, s0p, s1p,
+                              (int32_t *)list->p, n_out, e.stream, &D);
   else
     dev::EmitAggRelation(D, e.stream);
   if (defer) {

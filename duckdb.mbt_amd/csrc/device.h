@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "group_code.h"
+#include "group_direct_plan.h"
 #include "scan_codes.h"
 #include "vm.h"
 
@@ -96,9 +97,8 @@ void ScanEncode(const void *values, int phys, void *codes, int width, int64_t ba
 
 // --- fused GROUP BY on a small-range integer key (config C3) -------------
 // key in [kmin, kmin + nk) (the NULL group in slot nk - 1 when the key has
-// NULLs); up to 2 value columns of one phys.  vm: NULL-able columns (bit 0
-// value 0, bit 1 value 1, bit 2 the key); any: + the valid-row count tables
-size_t GroupDirectLds(int nk, int R, int nv, bool mm, int vm = 0);
+// NULLs); up to 2 value columns of one phys.  group_direct_plan.h decides how
+// it is launched.
 // validity words (LSB-first, 16-B aligned) of the NULL-able columns, or nullptr
 struct GroupValidity {
   const uint64_t *key, *v0, *v1;
@@ -107,7 +107,6 @@ struct GroupValidity {
 // rows with lo <= p <= lo + span for every entry.  src: 1 = its own column
 // `col` (int32/int64, loaded as an extra slice), 2 = the key column, 3 = value
 // column 0.
-#define GROUP_MAX_PRED 3
 struct GroupPred {
   int32_t src;
   int32_t phys;
@@ -117,38 +116,34 @@ struct GroupPred {
 };
 struct GroupPreds {
   int32_t n;
-  int32_t xcd;  // group_direct_lds: 1 = XCD-grouped step windows (blocks b, b+8, ... share an XCD)
+  int32_t xcd;  // group_direct_lds: 1 = XCD-grouped step windows (blocks b, b+8, ... share an XCD); the plan's
   GroupPred p[GROUP_MAX_PRED];
 };
-// Per-workgroup partial records of group_direct_lds (key-major, GroupPartialWords
-// u64 each: COUNT(*), then per value column its valid-row count, sum lo / hi
-// and, with MIN/MAX, min / max), reduced by GroupPartialsCompact.
-constexpr int kGroupPartialKeys = 128;
-__host__ __device__ constexpr int GroupPartialWords(int nv, bool mm) { return 1 + nv * (mm ? 5 : 3); }
-struct GroupPartialsOut {
-  void *buf;            // room for the records
-  size_t bytes;
-  int64_t state_slots;  // AggStates at st0 (st1 follows st0) that the call initialises when it uses atomics
-  bool used;            // set: the records were written (GroupPartialsCompact must follow)
-  int blocks;           // set: workgroups that wrote records
-};
-// The records reduced into cstar / st0 / st1 for every key (empty keys as
-// initialised), then the non-empty keys compacted as CompactSlots does; with
-// emit, the same launch then writes that relation as EmitAggRelation would
-// (emit->slot_list / n_list: slot_list / n_out).
+// The records of `blocks` workgroups (GroupDirectPlan::records, ::grid) reduced
+// into cstar / st0 / st1 for every key (empty keys as initialised), then the
+// non-empty keys compacted as CompactSlots does; with emit, the same launch
+// then writes that relation as EmitAggRelation would (emit->slot_list / n_list:
+// slot_list / n_out).
 struct EmitDesc;
-void GroupPartialsCompact(const GroupPartialsOut &po, int nv, bool mm, int nk, unsigned long long *count_star,
+void GroupPartialsCompact(const void *records, int blocks, int nv, bool mm, int nk, unsigned long long *count_star,
                           AggState *st0, AggState *st1, int32_t *slot_list, int64_t *n_out, hipStream_t s,
                           const EmitDesc *emit = nullptr);
-// false only when a predicate was given and the shape needs the segmented kernel.
-// po: the caller did not initialise cstar / st0 / st1: the call does (atomic
-// forms) or writes per-workgroup records instead (po->used).
-bool GroupByDirectStates(const void *kcol, int kphys, int64_t kmin, int nk, const void *v0, const void *v1, int vphys,
-                         int nv, bool mm, int64_t nrows, int64_t seg_rows, int R, unsigned long long *cstar,
-                         AggState *st0, AggState *st1, int grid_blocks, hipStream_t s,
-                         const GroupPreds *pred = nullptr, uint64_t vmaxabs = ~0ull /* (unused) */,
-                         const GroupValidity *valid = nullptr,  // NULL-able key / values: false if unsupported
-                         GroupPartialsOut *po = nullptr);
+struct GroupDirectArgs {
+  GroupDirectShape shape;  // what the plan was made for
+  const void *keys, *v0, *v1;
+  int64_t kmin;
+  GroupPreds preds;     // shape.npred of them
+  GroupValidity valid;  // the columns of shape.vm
+  unsigned long long *cstar;
+  AggState *st0, *st1;
+  // > 0: cstar and this many AggStates at st0 (st1 follows st0) are the
+  // launch's to initialise when it uses atomics; 0: the caller did
+  int64_t init_state_slots;
+  void *records;  // room for plan.record_bytes when plan.records
+};
+GroupDirectKnobs GroupDirectKnobsFromEnv();  // the MBX_GD_* switches
+// Launches plan.form (LdsOneFlush or Segmented; false for the others).
+bool GroupDirectLaunch(const GroupDirectArgs &a, const GroupDirectPlan &plan, hipStream_t s);
 
 // --- GROUP BY one integer key over a wide range (group_part.hip) ----------
 // Keys in [kmin, kmin + range) without NULLs, up to 2 value columns of one

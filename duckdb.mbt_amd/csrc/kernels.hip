@@ -1828,189 +1828,87 @@ __global__ __launch_bounds__(256) void group_direct_lds_kernel(const TK *__restr
   }
 }
 
-template <typename TK, typename TV, int NV, bool MM>
-static void LaunchGroupDirect(const void *k, const void *v0, const void *v1, int64_t n, int64_t kmin, int nk, int R,
-                              int64_t chunk, int64_t seg, unsigned long long *cstar, AggState *s0, AggState *s1,
-                              int grid, size_t lds, hipStream_t s) {
-  hipLaunchKernelGGL((group_direct_kernel<TK, TV, NV, MM>), dim3(grid), dim3(256), lds, s, (const TK *)k,
-                     (const TV *)v0, (const TV *)v1, n, kmin, nk, R, chunk, seg, cstar, s0, s1);
-  CHECK_LAUNCH();
+GroupDirectKnobs GroupDirectKnobsFromEnv() {
+  GroupDirectKnobs k;
+  const char *e = Knob("MBX_GD_VARIANT");
+  if (e && *e) {
+    int depth, gpc;
+    if (sscanf(e, "d%d_g%d", &depth, &gpc) == 2) {
+      k.depth = depth;
+      k.gpc = gpc;
+    } else {
+      k.seg = true;
+    }
+  }
+  if (const char *er = Knob("MBX_GD_R")) k.r_cap = atoi(er);
+  if (const char *ex = Knob("MBX_GD_XCD")) k.xcd = atoi(ex) != 0;
+  k.atomic_flush = Knob("MBX_GD_ATOMIC_FLUSH") != nullptr;
+  return k;
 }
 
-size_t GroupDirectLds(int nk, int R, int nv, bool mm, int vm) {
-  size_t nslot = (size_t)nk * R;
-  size_t b = (nslot * (vm ? 8 : 4) + 15) & ~(size_t)15;  // COUNT(*) (vm: + value 0's valid rows)
-  b += nslot * 8 * (size_t)(nv >= 2 ? 2 : 1);
-  if (mm) b += nslot * 8 * 2 * (size_t)(nv >= 2 ? 2 : 1);
-  if (vm) b += 4 * ((nslot + 3) & ~(size_t)3);  // valid-row counts of value column 1
-  return (b + 15) & ~(size_t)15;
-}
-
-bool GroupByDirectStates(const void *kcol, int kphys, int64_t kmin, int nk, const void *v0, const void *v1, int vphys,
-                         int nv, bool mm, int64_t nrows, int64_t seg_rows, int R, unsigned long long *cstar,
-                         AggState *st0, AggState *st1, int grid_blocks, hipStream_t s, const GroupPreds *pred,
-                         uint64_t vmaxabs, const GroupValidity *gvp, GroupPartialsOut *po) {
-  GroupValidity gv;
-  memset(&gv, 0, sizeof(gv));
-  if (gvp) gv = *gvp;
-  const int vm = (gv.v0 ? 1 : 0) | (gv.v1 ? 2 : 0) | (gv.key ? 4 : 0);
-  const bool vv = vm != 0;
-  if ((gv.v0 && nv < 1) || (gv.v1 && nv < 2)) return false;
-  if (po) po->used = false;
-  // with po, the states are this call's to initialise: the atomic forms below
-  // need them zeroed first, the partials form writes every one at the end
-  auto init_states = [&] {
-    if (po) InitAggStatesCounts(st0, po->state_slots, cstar, nk, s);
+// The kernels' template arguments resolved once from the shape: f is called
+// with tags of (TK, TV, NV, MM, DEPTH, VN).  COUNT only (nv == 0) has no value
+// type and no MIN / MAX: TV = int64_t, MM = false.
+template <typename T>
+struct GdType {
+  typedef T type;
+};
+template <typename F>
+static void GroupDirectDispatch(const GroupDirectShape &sh, int depth, F &&f) {
+  auto ring = [&](auto tk, auto tv, auto nv, auto mm) {
+    auto vn = [&](auto d) {
+      if (sh.vm) f(tk, tv, nv, mm, d, std::true_type());
+      else f(tk, tv, nv, mm, d, std::false_type());
+    };
+    if (depth == 3) vn(std::integral_constant<int, 3>());
+    else vn(std::integral_constant<int, 2>());
   };
-  if (nrows <= 0) {
-    init_states();
-    return true;
-  }
-  GroupPreds pr;
-  memset(&pr, 0, sizeof(pr));
-  if (pred) pr = *pred;
-  pr.xcd = 0;
-  if (const char *ex = Knob("MBX_GD_XCD")) pr.xcd = atoi(ex) != 0;
-  // LDS-DMA variant: one flush at the end, so a block's whole row share must
-  // fit the overflow bound the host derived (seg_rows) — else the segmented
-  // kernel below.  MBX_GD_VARIANT="d<2|3>_g<blocks per CU>" / "seg".
-  // Defaults from profiles/r02_group_sweep.log (after the table atomics stopped
-  // draining the DMA ring): d2_g1 for value aggregates (C3 1.735-1.77 ms, 2-6 %
-  // under d2_g3 on two boxes) and d2_g3 for COUNT-only tables (0.56 ms vs 0.62
-  // on the segmented kernel).
-  {
-    // NULL-able columns (vv): three 2-deep workgroups per CU -- the validity
-    // words' extra LDS reads and selects per step want more waves to hide
-    // them (C3 with NULLs 1.90 ms at d2_g3 vs 2.13 at d2_g2 and 2.32 at d2_g1,
-    // profiles/r06_gd_nulls/)
-    int depth = 2, gpc = nv > 0 ? ((gvp && (gvp->key || gvp->v0 || gvp->v1)) ? 3 : 1) : 3;
-    for (int j = 0; j < pr.n; j++)  // predicate slices of their own: a deeper ring (c3_where: d3 3.00 vs d2 3.32 ms)
-      if (pr.p[j].src == 1) depth = 3;
-    bool use = true;
-    const char *e = Knob("MBX_GD_VARIANT");
-    if (e && *e) use = sscanf(e, "d%d_g%d", &depth, &gpc) == 2 || pr.n != 0;
-    if (vv && !use) return false;  // the segmented kernel below has no validity words
-    // MBX_GD_R=<r>: fewer replicas (experiment; seg_rows scales with R)
-    if (const char *er = Knob("MBX_GD_R")) {
-      int r = atoi(er);
-      while (use && r > 0 && R > r) {
-        R >>= 1;
-        if (seg_rows > 0) seg_rows >>= 1;
-      }
+  auto values = [&](auto tk) {
+    auto cols = [&](auto tv) {
+      auto minmax = [&](auto nv) {
+        if (sh.mm) ring(tk, tv, nv, std::true_type());
+        else ring(tk, tv, nv, std::false_type());
+      };
+      if (sh.nv == 1) minmax(std::integral_constant<int, 1>());
+      else minmax(std::integral_constant<int, 2>());
+    };
+    if (sh.nv == 0) ring(tk, GdType<int64_t>(), std::integral_constant<int, 0>(), std::false_type());
+    else if (sh.val_bytes == 8) cols(GdType<int64_t>());
+    else cols(GdType<int32_t>());
+  };
+  if (sh.key_bytes == 4) values(GdType<int32_t>());
+  else values(GdType<int64_t>());
+}
+
+bool GroupDirectLaunch(const GroupDirectArgs &a, const GroupDirectPlan &p, hipStream_t s) {
+  const GroupDirectShape &sh = a.shape;
+  const bool seg = p.form == GroupDirectForm::Segmented;
+  if (!seg && p.form != GroupDirectForm::LdsOneFlush) return false;
+  // the atomic forms need the states zeroed first; the records form writes
+  // every one at the end (GroupPartialsCompact)
+  if (a.init_state_slots > 0 && !p.records) InitAggStatesCounts(a.st0, a.init_state_slots, a.cstar, sh.nk, s);
+  GroupPreds pr = a.preds;
+  pr.xcd = p.xcd;
+  unsigned long long *const gpart = p.records ? (unsigned long long *)a.records : nullptr;
+  GroupDirectDispatch(sh, p.depth, [&](auto tk, auto tv, auto nv, auto mm, auto depth, auto vn) {
+    typedef typename decltype(tk)::type TK;
+    typedef typename decltype(tv)::type TV;
+    constexpr int NV = decltype(nv)::value, DEPTH = decltype(depth)::value;
+    constexpr bool MM = decltype(mm)::value, VN = decltype(vn)::value;
+    if (seg) {
+      hipLaunchKernelGGL((group_direct_kernel<TK, TV, NV, MM>), dim3(p.grid), dim3(256), p.lds_bytes, s,
+                         (const TK *)a.keys, (const TV *)a.v0, (const TV *)a.v1, sh.n, a.kmin, sh.nk, p.R, p.chunk,
+                         p.seg_rows, a.cstar, a.st0, a.st1);
+      return;
     }
-    if (use) {
-      int grid = grid_blocks > 0 ? grid_blocks : NumCUs() * gpc;
-      int64_t nsteps = nrows >> 8;
-      int64_t waves = (int64_t)grid * 4;
-      int64_t rows_per_block = ((nsteps + waves - 1) / waves) * 4 * 256 + 256;
-      size_t tab = GroupDirectLds(nk, R, nv, mm, vm);
-      size_t ring_off = (tab + 15) & ~(size_t)15;
-      size_t slot = 256 * (size_t)(kphys == P_I64 ? 8 : 4) + (size_t)nv * 256 * (vphys == P_I64 ? 8 : 4) +
-                    (vv ? 3 * 32 : 0);
-      for (int j = 0; j < pr.n; j++)
-        if (pr.p[j].src == 1) slot += 256 * (size_t)(pr.p[j].phys == P_I64 ? 8 : 4);
-      depth = depth <= 2 ? 2 : 3;  // the kernel is built for 2- and 3-deep rings
-      const size_t lds_cap = gpc <= 1 ? 150 * 1024 : gpc == 2 ? 76 * 1024 : 64 * 1024;
-      size_t lds = ring_off + 4 * (size_t)depth * slot;
-      // wide slots (predicate slices): trade table replicas for ring space;
-      // seg_rows scales with R (rows per replica stay the same)
-      while (lds > lds_cap && R > 1) {
-        R >>= 1;
-        if (seg_rows > 0) seg_rows >>= 1;
-        tab = GroupDirectLds(nk, R, nv, mm, vm);
-        ring_off = (tab + 15) & ~(size_t)15;
-        lds = ring_off + 4 * (size_t)depth * slot;
-      }
-      // one flush at the end must be overflow-safe (else the segmented kernel)
-      const bool one_flush = seg_rows <= 0 || seg_rows >= rows_per_block;
-      // per-workgroup records reduced by group_partials_compact instead of the
-      // flush's global atomics (every workgroup hitting the same nk states at
-      // once): up to kGroupPartialKeys keys, when the caller gave room
-      unsigned long long *gpart = nullptr;
-      if (po && one_flush && lds <= lds_cap && nk <= kGroupPartialKeys &&
-          (size_t)nk * grid * GroupPartialWords(nv, mm) * 8 <= po->bytes && !Knob("MBX_GD_ATOMIC_FLUSH")) {
-        gpart = (unsigned long long *)po->buf;
-        po->used = true;
-        po->blocks = grid;
-      }
-      if (vv) {  // NULL-able columns: one flush only
-        if (!one_flush || lds > lds_cap) return false;
-        if (!gpart) init_states();
-#define GLVV(TK, TV, NV, MM, D)                                                                                     \
-  {                                                                                                                 \
-    (void)hipFuncSetAttribute((const void *)group_direct_lds_kernel<TK, TV, NV, MM, D, true>,                      \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);                              \
-    hipLaunchKernelGGL((group_direct_lds_kernel<TK, TV, NV, MM, D, true>), dim3(grid), dim3(256), lds, s,         \
-                       (const TK *)kcol, (const TV *)v0, (const TV *)v1, nrows, kmin, nk, R, ring_off, cstar, st0,  \
-                       st1, pr, gv, gpart);                                                                         \
-  }
-#define GLVN(TK, TV, MM, D)                                                                                       \
-  if (nv == 0) { GLVV(TK, TV, 0, false, D) }                                                                        \
-  else if (nv == 1) { GLVV(TK, TV, 1, MM, D) }                                                                      \
-  else { GLVV(TK, TV, 2, MM, D) }
-#define GLVVD(TK, TV)                                                                                             \
-  if (mm) { if (depth == 2) { GLVN(TK, TV, true, 2) } else { GLVN(TK, TV, true, 3) } }                              \
-  else { if (depth == 2) { GLVN(TK, TV, false, 2) } else { GLVN(TK, TV, false, 3) } }
-        if (kphys == P_I32) {
-          if (vphys == P_I64) { GLVVD(int32_t, int64_t) } else { GLVVD(int32_t, int32_t) }
-        } else {
-          if (vphys == P_I64) { GLVVD(int64_t, int64_t) } else { GLVVD(int64_t, int32_t) }
-        }
-#undef GLVVD
-#undef GLVN
-#undef GLVV
-        CHECK_LAUNCH();
-        return true;
-      }
-      if (one_flush && lds <= lds_cap) {
-        if (!gpart) init_states();
-#define GL(TK, TV, NV, MM, D)                                                                                      \
-  if (lds > 64 * 1024) /* deep rings at one or two blocks per CU */                                               \
-    (void)hipFuncSetAttribute((const void *)group_direct_lds_kernel<TK, TV, NV, MM, D, 0>,                         \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);                             \
-  hipLaunchKernelGGL((group_direct_lds_kernel<TK, TV, NV, MM, D, 0>), dim3(grid), dim3(256), lds, s,               \
-                     (const TK *)kcol, (const TV *)v0, (const TV *)v1, nrows, kmin, nk, R, ring_off, cstar, st0,   \
-                     st1, pr, gv, gpart);
-#define GLD(TK, TV, NV, MM) \
-  if (depth == 2) { GL(TK, TV, NV, MM, 2) } else { GL(TK, TV, NV, MM, 3) }
-#define GLV(TK, TV)                                                                      \
-  if (nv == 0) { GLD(TK, TV, 0, false) }                                                 \
-  else if (nv == 1) { if (mm) { GLD(TK, TV, 1, true) } else { GLD(TK, TV, 1, false) } } \
-  else { if (mm) { GLD(TK, TV, 2, true) } else { GLD(TK, TV, 2, false) } }
-        if (kphys == P_I32) {
-          if (vphys == P_I64) { GLV(int32_t, int64_t) } else { GLV(int32_t, int32_t) }
-        } else {
-          if (vphys == P_I64) { GLV(int64_t, int64_t) } else { GLV(int64_t, int32_t) }
-        }
-#undef GLV
-#undef GLD
-#undef GL
-        CHECK_LAUNCH();
-        return true;
-      }
-    }
-  }
-  if (pr.n) return false;  // a predicate needs the LDS-DMA kernel
-  init_states();
-  int grid = grid_blocks > 0 ? grid_blocks : NumCUs() * 4;
-  int64_t chunk = (nrows + grid - 1) / grid;
-  chunk = (chunk + 3) & ~(int64_t)3;
-  grid = (int)((nrows + chunk - 1) / chunk);
-  if (seg_rows <= 0 || seg_rows > chunk) seg_rows = chunk;
-  seg_rows = (seg_rows + 3) & ~(int64_t)3;
-  size_t lds = GroupDirectLds(nk, R, nv, mm);
-#define GD(TK, TV, NV, MM) LaunchGroupDirect<TK, TV, NV, MM>(kcol, v0, v1, nrows, kmin, nk, R, chunk, seg_rows, cstar, st0, st1, grid, lds, s)
-#define GDV(TK, TV)                         \
-  if (nv == 0) GD(TK, TV, 0, false);        \
-  else if (nv == 1) { if (mm) GD(TK, TV, 1, true); else GD(TK, TV, 1, false); } \
-  else { if (mm) GD(TK, TV, 2, true); else GD(TK, TV, 2, false); }
-  if (kphys == P_I32) {
-    if (vphys == P_I64) { GDV(int32_t, int64_t) } else { GDV(int32_t, int32_t) }
-  } else {
-    if (vphys == P_I64) { GDV(int64_t, int64_t) } else { GDV(int64_t, int32_t) }
-  }
-#undef GDV
-#undef GD
+    if (p.lds_bytes > 64 * 1024)  // deep rings at one or two workgroups per CU
+      (void)hipFuncSetAttribute((const void *)group_direct_lds_kernel<TK, TV, NV, MM, DEPTH, VN>,
+                                hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
+    hipLaunchKernelGGL((group_direct_lds_kernel<TK, TV, NV, MM, DEPTH, VN>), dim3(p.grid), dim3(256), p.lds_bytes, s,
+                       (const TK *)a.keys, (const TV *)a.v0, (const TV *)a.v1, sh.n, a.kmin, sh.nk, p.R, p.ring_off,
+                       a.cstar, a.st0, a.st1, pr, a.valid, gpart);
+  });
+  CHECK_LAUNCH();
   return true;
 }
 
@@ -2572,7 +2470,7 @@ __global__ __launch_bounds__(1024) void group_partials_compact_kernel(const unsi
   emit_agg_body(D, part, 0, 1);
 }
 
-void GroupPartialsCompact(const GroupPartialsOut &po, int nv, bool mm, int nk, unsigned long long *count_star,
+void GroupPartialsCompact(const void *records, int blocks, int nv, bool mm, int nk, unsigned long long *count_star,
                           AggState *st0, AggState *st1, int32_t *slot_list, int64_t *n_out, hipStream_t s,
                           const EmitDesc *emit) {
   EmitDesc D;
@@ -2580,7 +2478,7 @@ void GroupPartialsCompact(const GroupPartialsOut &po, int nv, bool mm, int nk, u
   else memset(&D, 0, sizeof(D));
 #define GPC(NV, MM)                                                                                               \
   hipLaunchKernelGGL((group_partials_compact_kernel<NV, MM>), dim3(1), dim3(1024), 0, s,                          \
-                     (const unsigned long long *)po.buf, po.blocks, nk, count_star, st0, st1, slot_list, n_out, D, \
+                     (const unsigned long long *)records, blocks, nk, count_star, st0, st1, slot_list, n_out, D,   \
                      emit ? 1 : 0)
   if (nv == 0) GPC(0, false);
   else if (nv == 1) { if (mm) GPC(1, true); else GPC(1, false); }

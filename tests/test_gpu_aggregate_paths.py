@@ -12,7 +12,16 @@ switched off (MBX_JIT=0) where the paths behind them are, so no list depends
 on how fast the compiler was.
 
 The kernel lists were recorded on the build before Aggregate() became a
-dispatcher; the dispatcher must reproduce them."""
+dispatcher; the dispatcher must reproduce them.
+
+Two forms of the direct GROUP BY's launch plan (csrc/group_direct_plan.h) have
+tables of their own, recorded on the build before the plan had a header:
+f2_segmented (values near 2^56 leave 4096 rows between flushes, fewer than a
+workgroup's share of 1 000 003 rows, so the segmented kernel runs) and
+f2_refused (1001 key slots with every column NULL-able and MIN / MAX do not
+fit beside the ring at three workgroups per CU: the launch is refused, which
+still leaves its group_direct entry in the profile, F3 is skipped and, with the
+run-time compiler off, group_assign and one group_reduce per aggregate answer)."""
 import numpy as np
 import pytest
 
@@ -98,6 +107,44 @@ def _grouped(keys, v, mask, aggs, names=None):
     return rows
 
 
+# ---- f2_segmented: 40 BIGINT keys, |v| up to 1000 * VS, just under 2^56 ----
+NSEG = 1_000_003
+VS = 72057594037927  # 2^56 // 1000
+TSEG_SQL = ("CREATE TABLE t AS SELECT (i * 31) % 40 AS k, ((i * 104729) % 2001 - 1000) * " + str(VS) + " AS v "
+            "FROM range({n}) tbl(i)")
+
+
+def _seg_rows(n):
+    """k, COUNT(*), SUM(v) in exact Python integers (the sums pass 2^63)"""
+    i = np.arange(n, dtype=np.int64)
+    k, c = (i * 31) % 40, (i * 104729) % 2001 - 1000
+    cnt, csum = np.bincount(k, minlength=40), np.zeros(40, dtype=np.int64)
+    np.add.at(csum, k, c)
+    return [[str(g), str(int(cnt[g])), str(int(csum[g]) * VS)] for g in range(40)]
+
+
+# ---- f2_refused: NULL-able INTEGER key of range 1000, two NULL-able BIGINT columns
+TREF_SQL = ("CREATE TABLE t AS SELECT "
+            "CASE WHEN i % 7 = 0 THEN NULL ELSE CAST((i * 31) % 1000 AS INTEGER) END AS kn, "
+            "CASE WHEN i % 5 = 0 THEN NULL ELSE (i * 104729) % 2000001 - 1000000 END AS yn, "
+            "CASE WHEN i % 11 = 0 THEN NULL ELSE (i * 17) % 1000 END AS wn FROM range({n}) tbl(i)")
+
+
+def _ref_rows(n):
+    """kn, SUM / MIN / MAX of yn and of wn over their non-NULL rows (NULL when a group has none), NULL key last"""
+    i = np.arange(n, dtype=np.int64)
+    kn = np.where(i % 7 == 0, 1000, (i * 31) % 1000)
+    cols = [(i % 5 != 0, (i * 104729) % 2000001 - 1000000), (i % 11 != 0, (i * 17) % 1000)]
+    rows = []
+    for g in np.unique(kn).tolist():
+        row = ["" if g == 1000 else str(g)]
+        for ok, v in cols:
+            sel = v[(kn == g) & ok]
+            row += [str(int(sel.sum())), str(int(sel.min())), str(int(sel.max()))] if len(sel) else ["", "", ""]
+        rows.append(row)
+    return rows
+
+
 ALL = slice(None)
 CSMM = ["count", "sum", "min", "max"]
 CS = ["count", "sum"]
@@ -122,6 +169,10 @@ CASES = {
                         ["group_direct"], True, lambda d: _grouped([d["kn"]], d["y"], ALL, CSMM)),
     "f2_where_third_column": (N, None, None, "SELECT k, COUNT(*), SUM(y) FROM t WHERE w < 500 GROUP BY k",
                               ["group_direct"], True, lambda d: _grouped([d["k"]], d["y"], d["w"] < 500, CS)),
+    "f2_segmented": (NSEG, None, None, "SELECT k, COUNT(*), SUM(v) FROM t GROUP BY k",
+                     ["group_direct"], True, lambda d: d),
+    "f2_refused": (N, None, "0", "SELECT kn, SUM(yn), MIN(yn), MAX(yn), SUM(wn), MIN(wn), MAX(wn) FROM t GROUP BY kn",
+                   ["group_direct", "group_assign"] + 6 * ["group_reduce"], True, lambda d: d),
     "f3_range_above_1024": (N, None, None, "SELECT kw, COUNT(*), SUM(y), MIN(y), MAX(y) FROM t GROUP BY kw",
                             ["group_part"], True, lambda d: _grouped([d["kw"]], d["y"], ALL, CSMM)),
     "f3_hashed": (NP, None, None, "SELECT ks, COUNT(*), SUM(y), MIN(y), MAX(y) FROM t GROUP BY ks",
@@ -147,6 +198,8 @@ CASES = {
                  ["filter_agg", "group_direct", "reduce_column"], True,
                  lambda d: [[str(len(np.unique(d["x"]))), str(int(d["x"].sum()))]]),
 }
+# the cases with a table of their own: its SQL and what the case's last entry is given
+TABLES = {"f2_segmented": (TSEG_SQL, _seg_rows), "f2_refused": (TREF_SQL, _ref_rows)}
 
 
 @pytest.mark.parametrize("case", list(CASES))
@@ -155,7 +208,8 @@ def test_path(mbx, monkeypatch, case):
     if jit is not None:
         monkeypatch.setenv("MBX_JIT", jit)
     c = _conn(mbx, min_rows)
-    q(c, T_SQL.format(n=n))
+    table, cols = TABLES.get(case, (T_SQL, _cols))
+    q(c, table.format(n=n))
     got = q(c, sql).rows
     prof = _profile(c)
     assert [kk["name"] for kk in prof] == kernels, (case, prof)
@@ -163,6 +217,6 @@ def test_path(mbx, monkeypatch, case):
         assert prof[0]["bytes"] == n, prof
     if case == "f1_zone_map_excluded":  # the entry of a scan that never ran
         assert prof[0]["bytes"] == 0, prof
-    rows = want(_cols(n))
+    rows = want(cols(n))
     assert (got if ordered else sorted(got)) == (rows if ordered else sorted(rows)), case
     c.close()
