@@ -1290,6 +1290,25 @@ DRel Aggregate(Engine &e, const DRel &src, const BoundSelect &s) {
   const int ng = (int)s.groups.size();
   const int na = (int)s.aggs.size();
   if (na > EMIT_MAX_AGGS) ThrowError("Not implemented", "too many aggregates in one query for the device path");
+  {  // VARCHAR predicates in WHERE, the keys or the arguments become BOOLEAN columns first
+    std::vector<BExprPtr> trees = s.groups;
+    for (auto &a : s.aggs) trees.push_back(a.arg);
+    trees.push_back(s.where);
+    DRel low;
+    if (LowerStringPredicates(e, src, trees, low)) {
+      // The bound plan stays as it is.  The aggregation reads only the WHERE,
+      // the keys and the aggregates of its select, so s2 carries just those;
+      // not being the statement's own select, it reads its group count back
+      // instead of leaving it on the device (CountMayStayOnDevice).
+      BoundSelect s2;
+      s2.is_agg = true;
+      s2.groups.assign(trees.begin(), trees.begin() + ng);
+      s2.aggs = s.aggs;
+      for (int j = 0; j < na; j++) s2.aggs[j].arg = trees[ng + j];
+      s2.where = trees[ng + na];
+      return Aggregate(e, low, s2);
+    }
+  }
   for (auto &a : s.aggs)
     if (a.distinct) return DistinctAggregate(e, src, s);
   DRel out;

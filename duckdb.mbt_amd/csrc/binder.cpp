@@ -15,6 +15,7 @@
 
 #include "engine.h"
 #include "plan.h"
+#include "str_match.h"
 
 namespace mbx {
 
@@ -450,7 +451,7 @@ static int Cmp3(const Value &a, const Value &b) {
       return x < y ? -1 : x > y ? 1 : 0;
     }
     case VC_STR:
-      return a.s < b.s ? -1 : a.s > b.s ? 1 : 0;
+      return StrCompare((const uint8_t *)a.s.data(), (int64_t)a.s.size(), (const uint8_t *)b.s.data(), (int64_t)b.s.size());
     default:
       if (a.type.id == T_INTERVAL) {
         i128 x = (i128)a.iv.months * 30 * 86400000000LL + (i128)a.iv.days * 86400000000LL + a.iv.micros;
@@ -459,6 +460,31 @@ static int Cmp3(const Value &a, const Value &b) {
       }
       return a.i < b.i ? -1 : a.i > b.i ? 1 : 0;
   }
+}
+
+void PlanStringMatch(const BExpr &e, StrMatchPlan *out) {
+  const std::string &pat = e.ch[1]->cval.s;
+  StrPlanStatus st;
+  if (e.op == B_LIKE) {
+    bool has_escape = false;
+    uint8_t escape = 0;
+    if (e.ch.size() > 2) {
+      const std::string &esc = e.ch[2]->cval.s;
+      if (esc.size() > 1)
+        ThrowError("Invalid Input", "Invalid escape string. Escape string must be empty or one character.");
+      has_escape = esc.size() == 1;
+      if (has_escape) escape = (uint8_t)esc[0];
+    }
+    st = PlanLike((const uint8_t *)pat.data(), (int64_t)pat.size(), has_escape, escape, out);
+  } else {
+    // prefix / suffix / contains: the constant is literal text
+    st = PlanStrCompare(SM_LIKE, (const uint8_t *)pat.data(), (int64_t)pat.size(), out);
+    out->form = e.op == B_PREFIX ? SF_PREFIX : e.op == B_SUFFIX ? SF_SUFFIX : SF_CONTAINS;
+  }
+  if (st == SP_TRAILING_ESCAPE) ThrowError("Invalid Input", "Like pattern must not end with escape character!");
+  if (st == SP_TOO_LONG)
+    ThrowError("Not implemented", "a VARCHAR match against a constant of more than " + std::to_string(kStrMatchCap) +
+                                      " bytes is not supported by the MI355X backend");
 }
 
 static i128 CheckedIntResult(BOp op, const LogicalType &t, i128 r, i128 a, i128 b, bool ovf) {
@@ -557,6 +583,11 @@ Value EvalConst(const BExpr &e) {
     case B_CONCAT: {
       Value r = Value::Varchar(a[0].s + a[1].s);
       return r;
+    }
+    case B_LIKE: case B_PREFIX: case B_SUFFIX: case B_CONTAINS: {
+      StrMatchPlan plan;
+      PlanStringMatch(e, &plan);
+      return Value::Bool(StrMatchRow(plan, (const uint8_t *)a[0].s.data(), (int64_t)a[0].s.size()));
     }
     case B_LENGTH: return Value::Int(T_BIGINT, (i128)a[0].s.size());
     case B_LOWER: return Value::Varchar(Lower(a[0].s));
@@ -716,6 +747,12 @@ std::string ExprToString(const BExpr &e) {
     case B_LENGTH: s = "length("; break;
     case B_LOWER: s = "lower("; break;
     case B_UPPER: s = "upper("; break;
+    case B_PREFIX: s = "prefix("; break;
+    case B_SUFFIX: s = "suffix("; break;
+    case B_CONTAINS: s = "contains("; break;
+    case B_LIKE:
+      return "(" + ExprToString(*e.ch[0]) + " LIKE " + ExprToString(*e.ch[1]) +
+             (e.ch.size() > 2 ? " ESCAPE " + ExprToString(*e.ch[2]) : "") + ")";
     case B_DISTINCT: return "(" + ExprToString(*e.ch[0]) + " IS DISTINCT FROM " + ExprToString(*e.ch[1]) + ")";
     case B_NOT_DISTINCT: return "(" + ExprToString(*e.ch[0]) + " IS NOT DISTINCT FROM " + ExprToString(*e.ch[1]) + ")";
     default:
@@ -890,6 +927,35 @@ BExprPtr BindArith(const std::string &opname, BExprPtr l, BExprPtr r) {
   return Fold(MkFunc(op, res, {CastTo(l, res), CastTo(r, res)}));
 }
 
+// s LIKE pattern [ESCAPE c], prefix / suffix / contains(s, x): the pattern side
+// must be constant; a NULL there makes the result NULL.  The pattern errors
+// are raised here, at bind.
+BExprPtr BindStringMatch(BOp op, const char *what, BExprPtr s, BExprPtr pat, BExprPtr esc) {
+  const LogicalType v(T_VARCHAR), b(T_BOOLEAN);
+  std::vector<BExprPtr> ch = {s->type.id == T_SQLNULL ? s : CastTo(s, v)};
+  bool null = ch[0]->kind == BExpr::CONST && ch[0]->cval.is_null;
+  for (BExprPtr c : {pat, esc}) {
+    if (!c) continue;
+    if (c->kind != BExpr::CONST)
+      ThrowError("Not implemented", std::string(what) + " with a non-constant pattern or escape is not supported by the MI355X backend");
+    null |= c->cval.is_null;
+    ch.push_back(c->cval.is_null ? c : CastTo(c, v));
+  }
+  if (null) {
+    auto n = MkConst(Value::Null(b));
+    n->type = b;
+    return n;
+  }
+  BExprPtr e = MkFunc(op, b, ch);
+  if (IsConstTree(*e)) return Fold(e);  // the folder plans the pattern, and raises its errors
+  if (ch[0]->kind != BExpr::COL)
+    ThrowError("Not implemented", std::string(what) + " over a string expression (" + ExprToString(*ch[0]) +
+                                      ") is not supported by the MI355X backend: only a VARCHAR column or a constant");
+  StrMatchPlan plan;
+  PlanStringMatch(*e, &plan);  // the pattern errors, at bind
+  return e;
+}
+
 BExprPtr BindAggregate(const Expr &e, BindCtx &ctx) {
   std::string n = Lower(e.name);
   if (!ctx.agg_mode || ctx.in_agg_arg)
@@ -985,6 +1051,14 @@ BExprPtr BindFunction(const Expr &e, BindCtx &ctx) {
     need(1);
     return Fold(MkFunc(n[0] == 'l' ? B_LOWER : B_UPPER, LogicalType(T_VARCHAR), {CastTo(args[0], LogicalType(T_VARCHAR))}));
   }
+  if (n == "starts_with" || n == "prefix" || n == "ends_with" || n == "suffix" || n == "contains") {
+    need(2);
+    BOp op = (n == "starts_with" || n == "prefix") ? B_PREFIX : n == "contains" ? B_CONTAINS : B_SUFFIX;
+    return BindStringMatch(op, n.c_str(), args[0], args[1], nullptr);
+  }
+  if (n == "like_escape" || n == "not_like_escape" || n == "ilike_escape" || n == "not_ilike_escape" ||
+      n == "regexp_matches" || n == "regexp_full_match" || n == "regexp_replace" || n == "regexp_extract" || n == "glob")
+    ThrowError("Not implemented", n + " is not supported by the MI355X backend");
   if (n == "mbx_synth") {
     // mbx_synth(seed, i, m) = splitmix64(seed + i) mod m  (synthetic column
     // generator of the benchmark configurations)
@@ -1142,6 +1216,13 @@ BExprPtr BindExprInner(const Expr &e, BindCtx &ctx) {
       BExprPtr lo = BindCompare(B_GE, x, BindExpr(*e.args[1], ctx), false, IsStrLit(*e.args[1]));
       BExprPtr hi = BindCompare(B_LE, x, BindExpr(*e.args[2], ctx), false, IsStrLit(*e.args[2]));
       BExprPtr r = Fold(MkFunc(B_AND, LogicalType(T_BOOLEAN), {lo, hi}));
+      if (e.negated) r = Fold(MkFunc(B_NOT, LogicalType(T_BOOLEAN), {r}));
+      return r;
+    }
+    case Expr::LIKE: {
+      BExprPtr s = BindExpr(*e.args[0], ctx), pat = BindExpr(*e.args[1], ctx);
+      BExprPtr esc = e.args.size() > 2 ? BindExpr(*e.args[2], ctx) : nullptr;
+      BExprPtr r = BindStringMatch(B_LIKE, "LIKE", s, pat, esc);
       if (e.negated) r = Fold(MkFunc(B_NOT, LogicalType(T_BOOLEAN), {r}));
       return r;
     }

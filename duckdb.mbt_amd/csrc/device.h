@@ -7,6 +7,7 @@
 #include "group_code.h"
 #include "group_direct_plan.h"
 #include "scan_codes.h"
+#include "str_match.h"
 #include "vm.h"
 
 namespace mbx {
@@ -230,6 +231,30 @@ void ScanLengths(const int64_t *lens, int64_t *offsets, int64_t n, hipStream_t s
 void StringCopy(const int64_t *codes, const uint64_t *valid, int64_t n, const int64_t *src_off, const char *src_chars,
                 const int64_t *pool_off, const char *pool_chars, const int64_t *out_off, char *out_chars,
                 hipStream_t s);
+
+// --- VARCHAR predicates (str_kernels.hip) -------------------------------------
+// A string column: offsets[n + 1] non-decreasing, row i = chars[offsets[i] ..
+// offsets[i + 1]); chars_len bytes of chars may be read; valid: validity words
+// or nullptr.
+struct StrCol {
+  const int64_t *offsets;
+  const char *chars;
+  int64_t chars_len;
+  const uint64_t *valid;
+};
+// out[i] = (row i of `a` matches `plan`) as one byte, 0 or 1, for i < n: the
+// layout of a BOOLEAN column.  The result of a NULL row is NULL: its byte is
+// whatever the row's bytes give and the caller lets the output share a.valid.
+// Only SM_DISTINCT / SM_NOT_DISTINCT read a.valid (NULL is a value there; the
+// output has no NULLs).  A wave step stages the chars of its 256 rows in LDS;
+// global_form: every step reads its rows straight from global memory instead,
+// the path the staged kernel takes by itself for a step over its LDS budget.
+void StrMatch(const StrMatchPlan &plan, const StrCol &a, int64_t n, uint8_t *out, bool global_form, hipStream_t s);
+// out[i] = a[i] OP b[i] for two columns of one relation (op: SM_EQ .. SM_NOT_DISTINCT).
+// out_valid (Words64(n) words, or nullptr) gets a.valid & b.valid when both
+// columns have NULLs and the operator can give NULL.
+void StrCompareCols(int op, const StrCol &a, const StrCol &b, int64_t n, uint8_t *out, uint64_t *out_valid,
+                    hipStream_t s);
 
 // --- ingest / stats ----------------------------------------------------------
 // min/max/null count over rows [0, n) of a fixed-width integer-like column.

@@ -297,6 +297,11 @@ void UploadHostColumn(Engine &e, const HostColumn &hc, int64_t n, DCol &d);
 DRel UploadRows(Engine &e, const std::vector<std::vector<Value>> &rows, const std::vector<LogicalType> &types);
 DCol AllocOut(Engine &e, const LogicalType &t, int64_t n, bool with_valid, bool zero_valid = true);
 DRel FilterProject(Engine &e, const DRel &rel, const BExprPtr &pred, const std::vector<BExprPtr> &exprs);
+// Evaluates every VARCHAR predicate leaf of `trees` (entries may be null) with
+// the str_match kernels into BOOLEAN columns appended to a copy of rel
+// (`lowered`) and rewrites the trees, copy on write, to read those columns.
+// false: no tree has such a leaf; trees and lowered are untouched.
+bool LowerStringPredicates(Engine &e, const DRel &rel, std::vector<BExprPtr> &trees, DRel &lowered);
 const BExpr *StripWidening(const BExpr *x);
 bool RangePredicate(const BExpr &p, int *col, i128 *lo, i128 *hi);
 bool RangeConj(const BExpr &p, std::map<int, std::pair<i128, i128>> &ranges);

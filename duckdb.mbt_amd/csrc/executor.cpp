@@ -307,12 +307,221 @@ static void MaterializeStrings(Engine &e, DCol &out, const DCol *src, const StrP
   out.data = nullptr;
 }
 
+// ---------------------------------------------------------------------------
+// VARCHAR predicates: lowered to BOOLEAN columns before the expression VM
+// ---------------------------------------------------------------------------
+// The VM has no string instructions.  A string predicate leaf -- a comparison
+// of a VARCHAR column with a VARCHAR constant (either order) or with another
+// VARCHAR column of the relation, B_LIKE, prefix / suffix / contains with a
+// constant -- is evaluated by the str_match kernels (str_kernels.hip) into a
+// one-byte-per-row BOOLEAN column appended to a copy of the relation, and the
+// tree is rebuilt with a reference to that column in the leaf's place.  The
+// bound plan itself is never changed: a prepared statement patches new
+// constants into its nodes, and the next execute must read them here.
+namespace {
+
+bool IsStrColumn(const DRel &rel, const BExpr &x) {
+  return x.kind == BExpr::COL && x.col >= 0 && x.col < (int)rel.cols.size() && !(rel.range && x.col == 0) &&
+         rel.cols[x.col].phys == P_STR && (rel.n == 0 || rel.cols[x.col].offsets) && ClassOf(x.type) == VC_STR;
+}
+bool IsStrConst(const BExpr &x) { return x.kind == BExpr::CONST && (ClassOf(x.type) == VC_STR || x.cval.is_null); }
+
+bool IsStrLeaf(const DRel &rel, const BExpr &x) {
+  if (x.kind != BExpr::FUNC) return false;
+  switch (x.op) {
+    case B_EQ: case B_NE: case B_LT: case B_LE: case B_GT: case B_GE: case B_DISTINCT: case B_NOT_DISTINCT: {
+      if (x.ch.size() != 2 || ClassOf(x.ch[0]->type) != VC_STR) return false;
+      const bool lc = IsStrColumn(rel, *x.ch[0]), rc = IsStrColumn(rel, *x.ch[1]);
+      return (lc && (rc || IsStrConst(*x.ch[1]))) || (rc && IsStrConst(*x.ch[0]));
+    }
+    case B_LIKE: case B_PREFIX: case B_SUFFIX: case B_CONTAINS: {
+      if (x.ch.size() < 2 || !IsStrColumn(rel, *x.ch[0])) return false;
+      for (size_t i = 1; i < x.ch.size(); i++)
+        if (!IsStrConst(*x.ch[i])) return false;
+      return true;
+    }
+    default:
+      return false;
+  }
+}
+
+// the same leaf: operator, columns and constant bytes
+bool SameStrLeaf(const BExpr &a, const BExpr &b) {
+  if (a.op != b.op || a.ch.size() != b.ch.size()) return false;
+  for (size_t i = 0; i < a.ch.size(); i++) {
+    const BExpr &x = *a.ch[i], &y = *b.ch[i];
+    if (x.kind != y.kind) return false;
+    if (x.kind == BExpr::COL ? x.col != y.col : (x.cval.is_null != y.cval.is_null || x.cval.s != y.cval.s)) return false;
+  }
+  return true;
+}
+
+BExprPtr BoolConst(bool v, bool is_null) {
+  auto c = std::make_shared<BExpr>();
+  c->kind = BExpr::CONST;
+  c->type = LogicalType(T_BOOLEAN);
+  c->cval = is_null ? Value::Null(c->type) : Value::Bool(v);
+  return c;
+}
+BExprPtr BoolFunc(BOp op, std::vector<BExprPtr> ch) {
+  auto f = std::make_shared<BExpr>();
+  f->kind = BExpr::FUNC;
+  f->op = op;
+  f->type = LogicalType(T_BOOLEAN);
+  f->ch = std::move(ch);
+  return f;
+}
+
+dev::StrCol StrColOf(const DCol &c) { return {c.offsets, c.chars, c.chars_len, c.validity}; }
+
+// MBX_STR_GLOBAL=1: every step of str_match reads its rows from global memory
+// (the A/B of tools/str_match_bench.py); read per launch so one process can alternate
+bool StrGlobalForm() {
+  const char *k = Knob("MBX_STR_GLOBAL");
+  return k && k[0] == '1';
+}
+
+struct StrLowering {
+  Engine &e;
+  const DRel &rel;
+  DRel out;  // rel + the BOOLEAN columns, once a leaf was lowered
+  bool lowered = false;
+  std::vector<std::pair<BExprPtr, BExprPtr>> done;  // leaf -> its replacement
+
+  StrLowering(Engine &en, const DRel &r) : e(en), rel(r) {}
+
+  // a BOOLEAN column for the kernels to fill; `share` lends its validity words
+  // (and what keeps them alive), so the result is NULL where that input is
+  DCol NewBool(const DCol *share) {
+    DCol d = AllocOut(e, LogicalType(T_BOOLEAN), rel.n, false);
+    if (share && share->validity) {
+      d.validity = share->validity;
+      d.owners.insert(d.owners.end(), share->owners.begin(), share->owners.end());
+      d.pins.insert(d.pins.end(), share->pins.begin(), share->pins.end());
+    }
+    return d;
+  }
+  BExprPtr Append(const DCol &d) {
+    if (!lowered) {
+      out = rel;
+      lowered = true;
+    }
+    out.cols.push_back(d);
+    auto c = std::make_shared<BExpr>();
+    c->kind = BExpr::COL;
+    c->col = (int)out.cols.size() - 1;
+    c->type = LogicalType(T_BOOLEAN);
+    return c;
+  }
+  void Match(const StrMatchPlan &plan, const DCol &c, DCol &d) {
+    ProfScope ps(e, "str_match", (double)rel.n * 9 + (double)c.chars_len, rel.n);
+    dev::StrMatch(plan, StrColOf(c), rel.n, (uint8_t *)d.data, StrGlobalForm(), e.stream);
+  }
+
+  BExprPtr Leaf(const BExpr &x) {
+    const bool distinct = x.op == B_DISTINCT || x.op == B_NOT_DISTINCT;
+    if (x.op == B_LIKE || x.op == B_PREFIX || x.op == B_SUFFIX || x.op == B_CONTAINS) {
+      for (size_t i = 1; i < x.ch.size(); i++)
+        if (x.ch[i]->cval.is_null) return BoolConst(false, true);
+      StrMatchPlan plan;
+      PlanStringMatch(x, &plan);
+      const DCol &c = rel.cols[x.ch[0]->col];
+      if (plan.form == SF_ALL) {  // true for every non-NULL row: nothing to launch
+        if (!c.validity) return BoolConst(true, false);
+        return BoolFunc(B_CASE, {BoolFunc(B_ISNOTNULL, {x.ch[0]}), BoolConst(true, false)});
+      }
+      DCol d = NewBool(&c);
+      Match(plan, c, d);
+      return Append(d);
+    }
+    const bool lc = x.ch[0]->kind == BExpr::COL, rc = x.ch[1]->kind == BExpr::COL;
+    const uint8_t op = x.op == B_EQ ? SM_EQ : x.op == B_NE ? SM_NE : x.op == B_LT ? SM_LT : x.op == B_LE ? SM_LE
+                       : x.op == B_GT ? SM_GT : x.op == B_GE ? SM_GE : x.op == B_DISTINCT ? SM_DISTINCT : SM_NOT_DISTINCT;
+    if (lc && rc) {
+      const DCol &a = rel.cols[x.ch[0]->col], &b = rel.cols[x.ch[1]->col];
+      const bool both = a.validity && b.validity && !distinct;
+      DCol d = NewBool(distinct || both ? nullptr : a.validity ? &a : &b);
+      if (both) {
+        auto v = Alloc(e, Words64(std::max<int64_t>(rel.n, 1)) * 8);
+        d.validity = (uint64_t *)v->p;
+        d.owners.push_back(v);
+      }
+      ProfScope ps(e, "str_match", (double)rel.n * 17 + (double)a.chars_len + (double)b.chars_len, rel.n);
+      dev::StrCompareCols(op, StrColOf(a), StrColOf(b), rel.n, (uint8_t *)d.data, both ? d.validity : nullptr, e.stream);
+      return Append(d);
+    }
+    const BExprPtr &colx = lc ? x.ch[0] : x.ch[1];
+    const BExpr &k = lc ? *x.ch[1] : *x.ch[0];
+    if (k.cval.is_null) {
+      // x <op> NULL is NULL; IS [NOT] DISTINCT FROM NULL is the column's NULL test
+      if (!distinct) return BoolConst(false, true);
+      return BoolFunc(x.op == B_DISTINCT ? B_ISNOTNULL : B_ISNULL, {colx});
+    }
+    StrMatchPlan plan;
+    if (PlanStrCompare(lc ? op : StrFlipOp(op), (const uint8_t *)k.cval.s.data(), (int64_t)k.cval.s.size(), &plan) != SP_OK)
+      ThrowError("Not implemented", "a VARCHAR comparison with a constant of more than " + std::to_string(kStrMatchCap) +
+                                        " bytes is not supported by the MI355X backend");
+    const DCol &c = rel.cols[colx->col];
+    DCol d = NewBool(distinct ? nullptr : &c);
+    Match(plan, c, d);
+    return Append(d);
+  }
+
+  BExprPtr Rewrite(const BExprPtr &x) {
+    if (!x || x->kind != BExpr::FUNC) return x;
+    if (IsStrLeaf(rel, *x)) {
+      for (auto &p : done)
+        if (SameStrLeaf(*p.first, *x)) return p.second;
+      BExprPtr r = Leaf(*x);
+      done.push_back({x, r});
+      return r;
+    }
+    std::vector<BExprPtr> ch;
+    bool changed = false;
+    for (auto &c : x->ch) {
+      ch.push_back(Rewrite(c));
+      changed |= ch.back() != c;
+    }
+    if (!changed) return x;
+    auto n = std::make_shared<BExpr>(*x);
+    n->ch = std::move(ch);
+    return n;
+  }
+};
+
+}  // namespace
+
+bool LowerStringPredicates(Engine &e, const DRel &rel, std::vector<BExprPtr> &trees, DRel &lowered) {
+  if (rel.n_dev) return false;  // only a column passthrough may follow (FilterProject)
+  StrLowering low(e, rel);
+  std::vector<BExprPtr> out;
+  bool changed = false;
+  for (auto &t : trees) {
+    out.push_back(low.Rewrite(t));
+    changed |= out.back() != t;
+  }
+  if (!changed) return false;
+  trees = std::move(out);
+  lowered = low.lowered ? low.out : rel;
+  return true;
+}
+
 static bool TryFilterCompact(Engine &e, const DRel &rel, const BExpr &pred, const std::vector<BExprPtr> &exprs,
                              DRel &out);
 
 // Evaluates `pred` (may be null) and `exprs` over `rel`; returns the
 // projected relation of the selected rows.
 DRel FilterProject(Engine &e, const DRel &rel, const BExprPtr &pred, const std::vector<BExprPtr> &exprs) {
+  {  // VARCHAR predicates become BOOLEAN columns of a copy of rel first
+    std::vector<BExprPtr> trees = exprs;
+    trees.push_back(pred);
+    DRel low;
+    if (LowerStringPredicates(e, rel, trees, low)) {
+      const BExprPtr p = trees.back();
+      trees.pop_back();
+      return FilterProject(e, low, p, trees);
+    }
+  }
   const int64_t n = rel.n;
   if (rel.n_dev) {  // only a column passthrough may carry a row count still on the device
     bool pt = !pred;

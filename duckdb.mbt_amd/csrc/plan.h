@@ -16,6 +16,8 @@ enum BOp : uint8_t {
   B_EQ, B_NE, B_LT, B_LE, B_GT, B_GE, B_DISTINCT, B_NOT_DISTINCT,
   B_AND, B_OR, B_NOT, B_ISNULL, B_ISNOTNULL,
   B_CAST, B_CASE, B_COALESCE, B_CONCAT, B_SYNTH, B_LENGTH, B_LOWER, B_UPPER,
+  // VARCHAR matches against a constant: ch = [string, pattern (, escape)] / [string, constant]
+  B_LIKE, B_PREFIX, B_SUFFIX, B_CONTAINS,
 };
 
 enum AggKind : uint8_t { A_COUNT_STAR, A_COUNT, A_SUM, A_MIN, A_MAX, A_AVG };
@@ -97,6 +99,12 @@ Value EvalConst(const BExpr &e);
 Value CastValue(const Value &v, const LogicalType &to, bool try_cast = false);
 LogicalType MaxType(const LogicalType &a, const LogicalType &b);  // implicit common super type
 bool IsConstTree(const BExpr &e);
+// The matcher plan (str_match.h) of a B_LIKE / B_PREFIX / B_SUFFIX / B_CONTAINS
+// node whose pattern (and escape) are non-NULL constants; raises LIKE's
+// pattern errors.  The binder's folder and the executor's lowering both plan
+// through here, so a pattern patched into a cached plan is checked again.
+struct StrMatchPlan;
+void PlanStringMatch(const BExpr &e, StrMatchPlan *out);
 std::string ExplainSelect(const BoundSelect &s, int indent = 0);
 std::string ExprToString(const BExpr &e);
 

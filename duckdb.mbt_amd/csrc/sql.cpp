@@ -560,7 +560,8 @@ class Parser {
       }
       bool neg = false;
       size_t save = p_;
-      if (IsKw("not") && (Peek().s == "between" || Peek().s == "in" || Peek().s == "like")) {
+      if (IsKw("not") && (Peek().s == "between" || Peek().s == "in" || Peek().s == "like" || Peek().s == "ilike" ||
+                          Peek().s == "similar" || Peek().s == "glob")) {
         p_++;
         neg = true;
       }
@@ -585,7 +586,19 @@ class Parser {
         l = e;
         continue;
       }
-      if (AcceptKw("like")) ThrowError("Not implemented", "LIKE is not supported by the MI355X backend");
+      if (AcceptKw("like")) {
+        auto e = Mk(Expr::LIKE);
+        e->negated = neg;
+        e->args = {l, ParseConcat()};
+        if (AcceptKw("escape")) e->args.push_back(ParseConcat());
+        l = e;
+        continue;
+      }
+      if (IsKw("ilike")) ThrowError("Not implemented", "ILIKE is not supported by the MI355X backend");
+      if (IsKw("similar") && Peek().s == "to")
+        ThrowError("Not implemented", "SIMILAR TO is not supported by the MI355X backend");
+      if (IsKw("glob") && Peek().k == Tok::STR)
+        ThrowError("Not implemented", "GLOB is not supported by the MI355X backend");
       p_ = save;
       break;
     }

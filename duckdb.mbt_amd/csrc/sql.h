@@ -42,6 +42,7 @@ struct Expr {
     ISNULL,    // args[0] IS [NOT] NULL  (negated)
     BETWEEN,   // args[0] [NOT] BETWEEN args[1] AND args[2]
     INLIST,    // args[0] [NOT] IN (args[1..])
+    LIKE,      // args[0] [NOT] LIKE args[1] [ESCAPE args[2]]
   };
   Kind kind = CONST;
   Value val;

@@ -289,7 +289,10 @@ struct VmCompiler {
       case B_EQ: case B_NE: case B_LT: case B_LE: case B_GT: case B_GE:
       case B_DISTINCT: case B_NOT_DISTINCT: {
         VClass cc = ClassOf(e.ch[0]->type);
-        if (cc == VC_STR) ThrowError("Not implemented", "VARCHAR comparisons are not supported on the MI355X device path");
+        // a VARCHAR column against a constant or another column never gets here (LowerStringPredicates)
+        if (cc == VC_STR)
+          ThrowError("Not implemented", "a VARCHAR comparison whose operand is a string expression (lower(s), s || 'x', a "
+                                        "cast) is not supported on the MI355X device path: " + ExprToString(e));
         if (e.ch[0]->type.id == T_INTERVAL) ThrowError("Not implemented", "INTERVAL comparisons are not supported on device");
         int a = Compile(*e.ch[0]), b = Compile(*e.ch[1]);
         if (e.op == B_DISTINCT || e.op == B_NOT_DISTINCT)
@@ -325,6 +328,10 @@ struct VmCompiler {
         return CheckArith(Step2(op, a, b), vc, t,
                           e.op == B_ADD ? E_OVF_ADD : e.op == B_SUB ? E_OVF_SUB : e.op == B_MUL ? E_OVF_MUL : E_OVF_NEG);
       }
+      case B_LIKE: case B_PREFIX: case B_SUFFIX: case B_CONTAINS:
+        // over a VARCHAR column these never get here (LowerStringPredicates)
+        ThrowError("Not implemented", "a VARCHAR match over anything but a VARCHAR column of the scanned relation is not "
+                                      "supported on the MI355X device path: " + ExprToString(e));
       default:
         ThrowError("Not implemented", "function " + ExprToString(e) + " is not supported on the MI355X device path");
     }
