@@ -1202,7 +1202,9 @@ static DRel SortRel(Engine &e, const DRel &r, const std::vector<BoundOrder> &ord
     if (c.phys == P_I128 || c.phys == P_INTERVAL)
       ThrowError("Not implemented", "ORDER BY a " + c.type.ToString() + " column is not supported on device yet");
     if (c.phys == P_STR) {
-      if (!c.offsets || !c.chars) ThrowError("Internal", "ORDER BY VARCHAR without materialised strings");
+      // (a column of empty strings and NULLs only has offsets and no character buffer: no chunk pass runs)
+      if (!c.offsets || (!c.chars && c.chars_len > 0))
+        ThrowError("Internal", "ORDER BY VARCHAR without materialised strings");
       dev::StrMaxLen(c.offsets, n, (unsigned long long *)e.d_scratch, e.stream);
       int64_t maxlen = ReadDev<int64_t>(e, e.d_scratch);
       for (int64_t ch = (maxlen + 7) / 8 - 1; ch >= 0; ch--) {

@@ -14,6 +14,7 @@
 #include <algorithm>
 #include <limits>
 #include <stdexcept>
+#include <string>
 #include <stdint.h>
 #include <type_traits>
 
@@ -60,6 +61,13 @@ typedef __int128 i128;
 typedef unsigned __int128 u128;
 
 #define CHECK_LAUNCH() (void)hipGetLastError()
+
+// hipCUB reports a refused launch or a bad argument through its return value:
+// a sort or scan that did not run must not pass for one that did
+static inline void CubCheck(hipError_t err, const char *what) {
+  if (err != hipSuccess) throw std::runtime_error(std::string("hipcub ") + what + ": " + hipGetErrorString(err));
+}
+#define CUB_CHECK(call, what) CubCheck((call), what)
 
 static int g_num_cus = 0;
 int NumCUs() {
@@ -236,10 +244,10 @@ void ScanTileCounts(const uint32_t *counts, int64_t *offsets, int64_t n, int64_t
   }
   hipcub::TransformInputIterator<int64_t, U32ToI64, const uint32_t *> it(counts, U32ToI64());
   size_t tmp = 0;
-  (void)hipcub::DeviceScan::ExclusiveSum(nullptr, tmp, it, offsets, (int)n, s);
+  CUB_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp, it, offsets, (int)n, s), "ExclusiveSum");
   void *d_tmp = nullptr;
   d_tmp = TempAlloc(tmp);
-  (void)hipcub::DeviceScan::ExclusiveSum(d_tmp, tmp, it, offsets, (int)n, s);
+  CUB_CHECK(hipcub::DeviceScan::ExclusiveSum(d_tmp, tmp, it, offsets, (int)n, s), "ExclusiveSum");
   TempFree(d_tmp, tmp);
   hipLaunchKernelGGL(scan_total_kernel, dim3(1), dim3(1), 0, s, counts, offsets, n, total);
 }
@@ -265,9 +273,9 @@ void ScanStepBits(const unsigned long long *bits, int64_t *offsets, int64_t step
   hipcub::CountingInputIterator<int64_t> idx(0);
   hipcub::TransformInputIterator<int64_t, StepPopc, hipcub::CountingInputIterator<int64_t>> it(idx, StepPopc{bits});
   size_t tmp = 0;
-  (void)hipcub::DeviceScan::ExclusiveSum(nullptr, tmp, it, offsets, (int)steps, s);
+  CUB_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp, it, offsets, (int)steps, s), "ExclusiveSum");
   void *d_tmp = TempAlloc(tmp);
-  (void)hipcub::DeviceScan::ExclusiveSum(d_tmp, tmp, it, offsets, (int)steps, s);
+  CUB_CHECK(hipcub::DeviceScan::ExclusiveSum(d_tmp, tmp, it, offsets, (int)steps, s), "ExclusiveSum");
   TempFree(d_tmp, tmp);
   hipLaunchKernelGGL(scan_bits_total_kernel, dim3(1), dim3(1), 0, s, bits, offsets, steps, total);
 }
@@ -2500,9 +2508,9 @@ void CompactSlots(const unsigned long long *count_star, int64_t nslots, int32_t 
   hipLaunchKernelGGL(slot_flags_kernel, dim3(grid), dim3(256), 0, s, count_star, nslots, flag);
   CHECK_LAUNCH();
   size_t tmp = 0;
-  (void)hipcub::DeviceScan::ExclusiveSum(nullptr, tmp, flag, pos, (int)nslots, s);
+  CUB_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp, flag, pos, (int)nslots, s), "ExclusiveSum");
   void *d_tmp = TempAlloc(tmp ? tmp : 16);
-  (void)hipcub::DeviceScan::ExclusiveSum(d_tmp, tmp, flag, pos, (int)nslots, s);
+  CUB_CHECK(hipcub::DeviceScan::ExclusiveSum(d_tmp, tmp, flag, pos, (int)nslots, s), "ExclusiveSum");
   hipLaunchKernelGGL(slot_scatter_kernel, dim3(grid), dim3(256), 0, s, flag, pos, nslots, slot_list, n_out);
   CHECK_LAUNCH();
   TempFree(d_tmp, tmp ? tmp : 16);
@@ -2525,8 +2533,13 @@ __global__ void sort_key_kernel(const void *col, int phys, const uint64_t *valid
     } else {
       int64_t lo, hi;
       load_phys(col, phys, r, lo, hi);
-      if (phys == P_F64 || phys == P_F32) k = f64_order(__longlong_as_double(lo));
-      else if (phys == P_U8 || phys == P_U16 || phys == P_U32 || phys == P_U64) k = (uint64_t)lo;
+      if (phys == P_F64 || phys == P_F32) {
+        // -0.0 = +0.0 for ORDER BY (as V_CMP_F has it); f64_order itself keeps
+        // them apart, which MIN / MAX rely on to round-trip the sign
+        double d = __longlong_as_double(lo);
+        if (d == 0) d = 0.0;
+        k = f64_order(d);
+      } else if (phys == P_U8 || phys == P_U16 || phys == P_U32 || phys == P_U64) k = (uint64_t)lo;
       else k = (uint64_t)lo ^ 0x8000000000000000ull;
       if (desc) k = ~k;
     }
@@ -2547,10 +2560,12 @@ void SortPairs(uint64_t *keys_in, int64_t *vals_in, uint64_t *keys_out, int64_t 
                int end_bit) {
   if (n <= 0) return;
   size_t tmp = 0;
-  (void)hipcub::DeviceRadixSort::SortPairs(nullptr, tmp, keys_in, keys_out, vals_in, vals_out, (int)n, 0, end_bit, s);
+  CUB_CHECK(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp, keys_in, keys_out, vals_in, vals_out, (int)n, 0, end_bit, s),
+            "SortPairs");
   void *d_tmp = nullptr;
   d_tmp = TempAlloc(tmp);
-  (void)hipcub::DeviceRadixSort::SortPairs(d_tmp, tmp, keys_in, keys_out, vals_in, vals_out, (int)n, 0, end_bit, s);
+  CUB_CHECK(hipcub::DeviceRadixSort::SortPairs(d_tmp, tmp, keys_in, keys_out, vals_in, vals_out, (int)n, 0, end_bit, s),
+            "SortPairs");
   TempFree(d_tmp, tmp);
 }
 
@@ -2701,10 +2716,10 @@ void ScanLengths(const int64_t *lens, int64_t *offsets, int64_t n, hipStream_t s
   (void)hipMemsetAsync(offsets, 0, sizeof(int64_t), s);
   if (n <= 0) return;
   size_t tmp = 0;
-  (void)hipcub::DeviceScan::InclusiveSum(nullptr, tmp, lens, offsets + 1, (int)n, s);
+  CUB_CHECK(hipcub::DeviceScan::InclusiveSum(nullptr, tmp, lens, offsets + 1, (int)n, s), "InclusiveSum");
   void *d_tmp = nullptr;
   d_tmp = TempAlloc(tmp);
-  (void)hipcub::DeviceScan::InclusiveSum(d_tmp, tmp, lens, offsets + 1, (int)n, s);
+  CUB_CHECK(hipcub::DeviceScan::InclusiveSum(d_tmp, tmp, lens, offsets + 1, (int)n, s), "InclusiveSum");
   TempFree(d_tmp, tmp);
 }
 
@@ -2960,10 +2975,10 @@ void HashGroupAssign(const HashKeys &k, int64_t n, unsigned long long *table, in
   hipLaunchKernelGGL(hash_occupancy_kernel, dim3(cgrid), dim3(256), 0, s, table, cap, flag);
   CHECK_LAUNCH();
   size_t tmp = 0;
-  (void)hipcub::DeviceScan::ExclusiveSum(nullptr, tmp, flag, pos, (int)cap, s);
+  CUB_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp, flag, pos, (int)cap, s), "ExclusiveSum");
   void *d_tmp = nullptr;
   d_tmp = TempAlloc(tmp ? tmp : 16);
-  (void)hipcub::DeviceScan::ExclusiveSum(d_tmp, tmp, flag, pos, (int)cap, s);
+  CUB_CHECK(hipcub::DeviceScan::ExclusiveSum(d_tmp, tmp, flag, pos, (int)cap, s), "ExclusiveSum");
   hipLaunchKernelGGL(hash_groups_kernel, dim3(cgrid), dim3(256), 0, s, table, flag, pos, cap, gid_of_entry, rep_row,
                      ngroups);
   CHECK_LAUNCH();

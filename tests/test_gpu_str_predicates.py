@@ -20,6 +20,7 @@ that the first 256 rows of the big tables end off a 16-byte boundary."""
 import pytest
 
 from conftest import q
+from gpu_tables import fill
 
 pytestmark = pytest.mark.gpu
 
@@ -107,23 +108,6 @@ def cell(v):
 
 
 # ---- tables ------------------------------------------------------------------
-def fill(c, name, cols, rows):
-    q(c, f"CREATE TABLE {name} ({cols})")
-    ap = c.create_appender("main", name).value
-    for row in rows:
-        ap.begin_row()
-        for k, v in enumerate(row):
-            if v is None:
-                ap.append_null()
-            elif isinstance(v, str):
-                ap.append_varchar(v)
-            else:
-                ap.append_int(v)
-        ap.end_row()
-    ap.flush()
-    ap.close()
-
-
 class Db:
     pass
 

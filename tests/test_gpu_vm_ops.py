@@ -4,14 +4,12 @@ kernels (MBX_JIT=sync: jit_filter / jit_project), against the exact model of
 tests/vm_reference.py over the tables of tests/vm_cases.py.  Integers,
 decimals and booleans are compared as text, DOUBLE and FLOAT by bit pattern
 (any NaN matches NaN; -0.0 and +0.0 differ)."""
-import struct
-
-import numpy as np
 import pytest
 
 import vm_cases as V
 import vm_reference as R
 from conftest import q
+from gpu_tables import _f64, load
 
 pytestmark = pytest.mark.gpu
 
@@ -29,45 +27,6 @@ def _conn(mbx):
 
 def _kernels(c):
     return [k["name"] for k in c.last_profile()["kernels"]]
-
-
-def _f64(raw):
-    return struct.unpack("<d", raw)[0] if len(raw) == 8 else struct.unpack("<f", raw)[0]
-
-
-def load(mbx, conn, table, name, rows, cols):
-    """table `name` with the given rows of the given columns, through the
-    columnar appender; then read back: the load itself must be exact"""
-    cols = [table.cols[k] for k in cols]
-    q(conn, f"CREATE TABLE {name} (" + ", ".join(f"{c.name} {c.sqltype}" for c in cols) + ")")
-    ap = conn.create_appender("main", name).value
-    idx = np.array(rows, dtype=np.int64)
-    for j, c in enumerate(cols):
-        valid = np.array(c.valid, dtype=np.uint8)[idx]
-        r = ap.append_column(j, c.numpy()[idx], None if valid.all() else valid)
-        assert isinstance(r, mbx.Ok), r.error.message
-    r = ap.commit(len(rows))
-    assert isinstance(r, mbx.Ok), r.error.message
-    ap.close()
-    res = conn.query_raw(f"SELECT * FROM {name}")
-    assert res.row_count() == len(rows)
-    text, nulls = res.cells()
-    for j, c in enumerate(cols):
-        for k, r in enumerate(rows):
-            v = c.get(r)
-            assert nulls[k][j] == (v is None), (name, c.name, r)
-            if v is None:
-                continue
-            if c.kind in ("f64", "f32"):
-                got = _f64(res.raw(j, k))
-                assert (got != got) if v != v else R.bits(got) == R.bits(v), (name, c.name, r, got, v)
-            elif c.kind == "dec":
-                assert text[k][j] == V.dec_text(v, c.scale), (name, c.name, r, text[k][j])
-            elif c.kind == "bool":
-                assert text[k][j] == ("true" if v else "false"), (name, c.name, r)
-            else:
-                assert text[k][j] == str(v), (name, c.name, r, text[k][j])
-    res.close()
 
 
 def check_projection(conn, cases, source, rows, where=None):

@@ -43,7 +43,7 @@ class Col:
         else:
             dt = {"TINYINT": np.int8, "SMALLINT": np.int16, "INTEGER": np.int32, "BIGINT": np.int64,
                   "UTINYINT": np.uint8, "USMALLINT": np.uint16, "UINTEGER": np.uint32, "UBIGINT": np.uint64,
-                  "HUGEINT": None}[t]
+                  "HUGEINT": None, "DATE": np.int32, "TIMESTAMP": np.int64}[t]  # days / microseconds
         if dt is None:  # 128 bits: low word, high word
             return np.array([[v & (2 ** 64 - 1), (v >> 64) & (2 ** 64 - 1)] for v in self.values], dtype=np.uint64)
         return np.array(self.values, dtype=dt)
