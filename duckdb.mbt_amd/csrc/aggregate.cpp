@@ -987,15 +987,15 @@ static bool ScanAggregate(Engine &e, const DRel &src, const BoundSelect &s, DRel
     bool need_mm = false;
     for (auto &a : s.aggs) need_mm |= a.kind == A_MIN || a.kind == A_MAX;
     if (by_codes) {
-      const ScanCodeRange cr = PlanScanCodeRange(tc->code_width, (i128)tc->code_base, tc->imax, (int64_t)lo, (int64_t)hi);
+      const ScanCodeRange cr = PlanScanFieldRange(tc->code_fields, (i128)tc->code_base, tc->imax, (int64_t)lo, (int64_t)hi);
       if (cr.empty) {
         // the zone map rules every row out: no scan (the entry keeps the
         // profile at one filter_agg per statement, with nothing read)
         ProfScope ps(e, "filter_agg", 0, src.n);
         dev::InitAggStatesCounts(st, 1, cstar, 1, e.stream);
       } else {
-        ProfScope ps(e, "filter_agg", (double)src.n * tc->code_width, src.n);
-        npartials = dev::FilterAggCodes(tc->codes, tc->code_width, tc->code_base, cr.clo, cr.cspan, cr.packed,
+        ProfScope ps(e, "filter_agg", (double)ScanCodeBytes(tc->code_fields, src.n), src.n);
+        npartials = dev::FilterAggCodes(tc->codes, tc->code_fields, tc->code_base, cr.clo, cr.cspan, cr.form,
                                         A != nullptr, need_mm, src.n, e.d_partials, e.stream);
       }
     } else if (P) {

@@ -85,15 +85,17 @@ int FilterMultiPartials(const FilterMultiDesc &d, int64_t nrows, AggPartial *par
 int FilterAggStates(const void *pcol, int pphys, int64_t lo, int64_t hi, bool has_pred, const void *acol, int aphys,
                     int64_t nrows, AggState *st, unsigned long long *cstar, int grid_blocks, hipStream_t s,
                     bool need_minmax = true, uint64_t sum_maxabs = ~0ull, AggPartial *partials = nullptr);
-// The same over a column's code image (scan_codes.h): `width`-byte codes of
-// value - base, predicate clo <= code <= clo + cspan (PlanScanCodeRange).
+// The same over a column's code image (scan_codes.h): `fields` codes of
+// value - base per 32-bit word, predicate clo <= code <= clo + cspan compared
+// by `form` (a word-parallel ScanCompare, both from PlanScanFieldRange).
 // sum = false: COUNT(*) only; else COUNT / SUM (and MIN / MAX) of the passing
 // values.  Always writes per-workgroup partials and returns their count (> 0).
-int FilterAggCodes(const void *codes, int width, int64_t base, uint32_t clo, uint32_t cspan, bool packed, bool sum,
+int FilterAggCodes(const void *codes, int fields, int64_t base, uint32_t clo, uint32_t cspan, int form, bool sum,
                    bool need_minmax, int64_t nrows, AggPartial *partials, hipStream_t s);
-// codes[i] = (uint<width>)(values[i] - base) for rows [begin, end) of a P_I32 /
-// P_I64 column (both buffers 256-B aligned at row 0)
-void ScanEncode(const void *values, int phys, void *codes, int width, int64_t base, int64_t begin, int64_t end,
+// Rebuilds from the values of a P_I32 / P_I64 column every word of its code
+// image that holds a row of [begin, end): words begin / fields to
+// ceil(end / fields) - 1 (both buffers 256-B aligned at row 0)
+void ScanEncode(const void *values, int phys, void *codes, int fields, int64_t base, int64_t begin, int64_t end,
                 hipStream_t s);
 
 // --- fused GROUP BY on a small-range integer key (config C3) -------------

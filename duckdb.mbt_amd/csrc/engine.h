@@ -42,15 +42,16 @@ struct DevColumn {
   i128 imin = 0, imax = 0;
   int64_t null_count = 0;
   // code image (scan_codes.h) of a narrow-range P_I32 / P_I64 column without
-  // NULLs: codes[i] = (uint<code_width * 8>)(value[i] - code_base) for rows
-  // [0, code_rows), in its own 256-B-aligned buffer.  Built at ingest once the
-  // zone map is folded, extended by appends that fit the base and width,
-  // rebuilt when the base moves, freed when the range outgrows the width.  The
+  // NULLs: value[i] - code_base for rows [0, code_rows), code_fields to a 32-bit
+  // word, in its own 256-B-aligned buffer of ceil(code_cap / code_fields) words.
+  // Built at ingest once the zone map is folded, extended by appends that fit
+  // the base and the field width, rebuilt when the base moves or the field
+  // width changes, freed when the range outgrows two bytes.  The
   // fused filter-aggregate streams it in place of the values when code_rows
   // covers the table; `data` stays the column's truth for every other reader.
   void *codes = nullptr;
   std::shared_ptr<void> codes_owner;
-  int code_width = 0;  // 0: no image
+  int code_fields = 0;  // codes per word (ScanCodeFields), 0: no image
   int64_t code_base = 0, code_rows = 0, code_cap = 0;
 };
 
@@ -169,12 +170,16 @@ struct Options {
   // "mbx_shard_rows": appends fill part i of a sharded table up to this many
   // rows before moving on to part i + 1 (0: appends go to the last part)
   int64_t shard_rows = 0;
-  // "mbx_scan_codes": keep a 1- or 2-byte code image of narrow-range integer
+  // "mbx_scan_codes": keep a code image (1 to 16 bits a row) of narrow-range integer
   // columns and scan it in the fused filter-aggregate (false: none is built)
   bool scan_codes = true;
   // "mbx_scan_codes_min_rows": tables below this many rows get no image (their
   // scan is launch-bound: 2^20 rows of 8 bytes stream in ~1 us)
   int64_t scan_codes_min_rows = (int64_t)1 << 20;
+  // "mbx_scan_codes_bits_min_rows": tables below this many rows keep whole
+  // bytes for a range that fits 8 bits (packing 1..6-bit fields saves at most
+  // 0.2 B a row: 3.4 MB, under 0.5 us of streaming, at 2^24 rows)
+  int64_t scan_codes_bits_min_rows = (int64_t)1 << 24;
   // "mbx_force_peer" (tests): shards on the same device still exchange row
   // results by peer DMA (hipMemcpyPeerAsync), as distinct devices do
   bool force_peer = false;

@@ -101,41 +101,47 @@ static void Grow(Engine &e, DevColumn &c, int64_t nrows_old, int64_t need) {
 
 // Brings c's code image (scan_codes.h) up to nrows rows, once the zone map of
 // every row is folded: the appended tail when the map still fits the image's
-// base and width, all rows when the base or the width changed, and no image
-// when the column does not qualify.  A column is never left partly coded
-// beyond this call: code_rows is nrows or the image is gone.
+// base and field width, all rows when the base or the field width changed
+// (the table growing past mbx_scan_codes_bits_min_rows changes it once), and
+// no image when the column does not qualify.  The word that holds the first
+// appended row is rebuilt whole from the values, never read back.  A column is
+// never left partly coded beyond this call: code_rows is nrows or the image
+// is gone.
 void UpdateScanCodes(Engine &e, DevColumn &c, int64_t nrows) {
-  int w = 0;
+  int f = 0;
   if (e.scan_codes && nrows > 0 && nrows >= e.scan_codes_min_rows && c.stats_valid && !c.validity &&
       c.null_count == 0 && c.data)
-    w = ScanCodeWidth(c.phys, c.imin, c.imax);
-  if (!w) {
+    f = ScanCodeFields(c.phys, c.imin, c.imax, nrows >= e.scan_codes_bits_min_rows);
+  if (!f) {
     c.codes = nullptr;
     c.codes_owner.reset();
-    c.code_width = 0;
+    c.code_fields = 0;
     c.code_base = c.code_rows = c.code_cap = 0;
     return;
   }
-  const bool extend = c.codes && c.code_width == w && c.code_base == (int64_t)c.imin && c.code_rows <= nrows;
+  const bool extend = c.codes && c.code_fields == f && c.code_base == (int64_t)c.imin && c.code_rows <= nrows;
   const int64_t begin = extend ? c.code_rows : 0;
   if (begin == nrows) return;
   if (!extend || c.code_cap < nrows) {
     const int64_t cap = std::max<int64_t>(nrows, c.capacity);
     void *nc = nullptr;
-    HIPCHK(hipMalloc(&nc, (size_t)cap * w));
+    HIPCHK(hipMalloc(&nc, (size_t)((ScanCodeWords(f, cap) * 4 + 255) & ~(int64_t)255)));
     if (begin > 0) {
-      HIPCHK(hipMemcpyAsync(nc, c.codes, (size_t)begin * w, hipMemcpyDeviceToDevice, e.stream));
+      HIPCHK(hipMemcpyAsync(nc, c.codes, (size_t)ScanCodeWords(f, begin) * 4, hipMemcpyDeviceToDevice, e.stream));
       HIPCHK(hipStreamSynchronize(e.stream));  // before the old image goes
     }
     c.codes_owner = DevOwned(e, nc);
     c.codes = nc;
     c.code_cap = cap;
-    c.code_width = w;
+    c.code_fields = f;
     c.code_base = (int64_t)c.imin;
   }
   {
-    ProfScope ps(e, "scan_encode", (double)(nrows - begin) * (PhysSize(c.phys) + w), nrows - begin);
-    dev::ScanEncode(c.data, c.phys, c.codes, w, c.code_base, begin, nrows, e.stream);
+    const int64_t first = begin / f * f;  // the first row of the first rebuilt word
+    ProfScope ps(e, "scan_encode",
+                 (double)(nrows - first) * PhysSize(c.phys) + (double)(ScanCodeBytes(f, nrows) - ScanCodeBytes(f, first)),
+                 nrows - first);
+    dev::ScanEncode(c.data, c.phys, c.codes, f, c.code_base, begin, nrows, e.stream);
   }
   c.code_rows = nrows;
 }

@@ -589,30 +589,37 @@ __global__ __launch_bounds__(256) void filter_agg_lds_kernel(const T *__restrict
   }
 }
 
-// The same ring over a column's code image (scan_codes.h): W-byte codes
-// (value - base), a 1-KiB piece is 1024 / W rows, 16 / W codes per lane.  The
-// predicate is clo <= code <= clo + cspan.  MODE 2 counts; MODE 0 also sums the
-// passing codes (and, MM, takes their min / max).  PACKED (every code of the
-// column below 128 / 32768): the compare runs on whole 32-bit words
-// (ScanPackedMask), the count is a popcount and the sum a masked v_sad_u8.
-// Per piece a lane adds at most 16 x 65535 to 32-bit piece totals, folded into
-// 64-bit lane totals; the value sum is codes + count x base in int128, once
-// per lane, so the partial records are exactly those of the 8-byte kernel.
-template <int W, int MODE, int DEPTH, bool MM, bool PACKED>
-__global__ __launch_bounds__(256) void filter_agg_codes_kernel(const unsigned char *__restrict__ codes, int64_t n,
+// The same ring over a column's code image (scan_codes.h): F codes of
+// value - base per 32-bit word in fields of Bf = 32 / F bits, a 1-KiB piece is
+// 256 F rows, 4 F codes per lane.  The predicate is clo <= code <= clo + cspan.
+// MODE 2 counts; MODE 0 also sums the passing codes.  FORM (ScanCompare, chosen
+// by PlanScanFieldRange) is the compare: a word-parallel one leaves one bit per
+// passing field, the count is a popcount, and the sum adds the masked word's
+// even and odd fields into 2 Bf-bit lanes that are folded once per piece (four
+// words: at most 4 (2^Bf - 1) per lane; a 1-bit code sums by popcount, a byte
+// by v_sad_u8).  SC_PER_CODE extracts every field and also takes the passing
+// codes' min / max.  Per piece a lane adds at most 16 x 65535 to 32-bit piece
+// totals, folded into 64-bit lane totals; the value sum is codes + count x base
+// in int128, once per lane, so the partial records are exactly those of the
+// 8-byte kernel.
+template <int F, int MODE, int DEPTH, int FORM>
+__global__ __launch_bounds__(256) void filter_agg_codes_kernel(const uint32_t *__restrict__ codes, int64_t n,
                                                                uint32_t clo, uint32_t cspan, int64_t base,
                                                                AggPartial *partials) {
-  constexpr int64_t RP = 1024 / W;
-  constexpr int CPW = 4 / W;  // codes per 32-bit word
+  constexpr int BF = ScanFieldBits(F);
+  constexpr int64_t RP = ScanPieceRows(F);
+  constexpr bool MM = FORM == SC_PER_CODE;
+  constexpr uint32_t EVEN = ScanEvenFields(F);
   __shared__ __attribute__((aligned(16))) v4i32 ring[4 * DEPTH * 64];
   static_assert(sizeof(v4i32) * 4 * DEPTH * 64 >= 4 * sizeof(Acc), "the block reduction reuses the ring");
+  static_assert(F * BF <= 32 && 16ull * F * ScanFieldMax(F) < (1ull << 32), "a piece's totals fit 32 bits");
   const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int64_t npieces = n / RP;
   const int64_t nw = (int64_t)gridDim.x * 4;
   int64_t pc = (int64_t)blockIdx.x * 4 + w;
   v4i32 *slot0 = ring + w * DEPTH * 64;
   const v4i32 *P = (const v4i32 *)codes;
-  const uint32_t H = ScanPackedTop(W), PA = ScanPackedA(W, PACKED ? clo : 0), PB = ScanPackedB(W, PACKED ? clo + cspan : 0);
+  const ScanWordCmp K = ScanWordCmpOf(F, FORM, clo, clo + cspan);
   uint64_t cnt = 0, sum = 0;
   int32_t mn = INT32_MAX, mx = -1;  // codes are below 2^16
   auto one = [&](uint32_t c, uint32_t &pcnt, uint32_t &psum) {
@@ -624,21 +631,38 @@ __global__ __launch_bounds__(256) void filter_agg_codes_kernel(const unsigned ch
       mx = max(mx, ok ? (int32_t)c : -1);
     }
   };
-  auto word = [&](uint32_t x, uint32_t &pcnt, uint32_t &psum) {
-    if (PACKED && !MM) {
-      const uint32_t m = ScanPackedMask(x, PA, PB, H);
+  // ev / od: the piece's passing codes of the even and the odd fields, in lanes of 2 BF bits
+  auto word = [&](uint32_t x, uint32_t &pcnt, uint32_t &psum, uint32_t &ev, uint32_t &od) {
+    if (FORM != SC_PER_CODE) {
+      const uint32_t m = ScanWordMask(FORM, x, K);
       pcnt += __builtin_popcount(m);
       if (MODE == 0) {
-        if (W == 1) {
-          psum = __builtin_amdgcn_sad_u8(x & ((m >> 7) * 0xFFu), 0u, psum);
+        if (BF == 1) {
+          psum += __builtin_popcount(x & m);
+        } else if (BF == 8) {
+          psum = __builtin_amdgcn_sad_u8(x & ScanFieldsOf(F, m), 0u, psum);
         } else {
-          const uint32_t t = x & ((m >> 15) * 0xFFFFu);
-          psum += (t & 0xFFFFu) + (t >> 16);
+          const uint32_t t = x & ScanFieldsOf(F, m);
+          ev += t & EVEN;
+          od += (t >> BF) & EVEN;
         }
       }
     } else {
 #pragma unroll
-      for (int e = 0; e < CPW; e++) one(W == 1 ? (x >> (8 * e)) & 0xFFu : (x >> (16 * e)) & 0xFFFFu, pcnt, psum);
+      for (int e = 0; e < F; e++) one((x >> (BF * e)) & ScanFieldMax(F), pcnt, psum);
+    }
+  };
+  auto fold = [&](uint32_t ev, uint32_t od, uint32_t &psum) {
+    if (MODE != 0 || FORM == SC_PER_CODE || BF == 1 || BF == 8) return;
+    if (BF == 2) {  // a 4-bit lane holds 4 x 3, not 8 x 3: fold the two halves apart
+#pragma unroll
+      for (int e = 0; e < 8; e++) psum += ((ev >> (4 * e)) & 0xFu) + ((od >> (4 * e)) & 0xFu);
+    } else if constexpr (BF == 16) {
+      psum += ev + od;
+    } else {
+      const uint32_t t = ev + od;
+#pragma unroll
+      for (int e = 0; e < (F + 1) / 2; e++) psum += (t >> (2 * BF * e)) & ((1u << (2 * BF)) - 1u);
     }
   };
 #pragma unroll
@@ -655,11 +679,12 @@ __global__ __launch_bounds__(256) void filter_agg_codes_kernel(const unsigned ch
     int64_t q = pc + DEPTH * nw;
     q = q < npieces ? q : pc;  // past the end: re-read the piece just consumed
     __builtin_amdgcn_global_load_lds((const void *)(P + q * 64 + lane), (void *)(slot0 + k * 64), 16, 0, 2);
-    uint32_t pcnt = 0, psum = 0;
-    word((uint32_t)x.x, pcnt, psum);
-    word((uint32_t)x.y, pcnt, psum);
-    word((uint32_t)x.z, pcnt, psum);
-    word((uint32_t)x.w, pcnt, psum);
+    uint32_t pcnt = 0, psum = 0, ev = 0, od = 0;
+    word((uint32_t)x.x, pcnt, psum, ev, od);
+    word((uint32_t)x.y, pcnt, psum, ev, od);
+    word((uint32_t)x.z, pcnt, psum, ev, od);
+    word((uint32_t)x.w, pcnt, psum, ev, od);
+    fold(ev, od, psum);
     cnt += pcnt;
     sum += psum;
     k = k + 1 == DEPTH ? 0 : k + 1;
@@ -667,8 +692,7 @@ __global__ __launch_bounds__(256) void filter_agg_codes_kernel(const unsigned ch
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   if (blockIdx.x == 0 && w == 0) {
     uint32_t pcnt = 0, psum = 0;
-    for (int64_t i = npieces * RP + lane; i < n; i += 64)
-      one(W == 1 ? (uint32_t)codes[i] : (uint32_t)((const uint16_t *)codes)[i], pcnt, psum);
+    for (int64_t i = npieces * RP + lane; i < n; i += 64) one(ScanCodeAt(codes, F, i), pcnt, psum);
     cnt += pcnt;
     sum += psum;
   }
@@ -693,50 +717,65 @@ __global__ __launch_bounds__(256) void filter_agg_codes_kernel(const unsigned ch
   }
 }
 
-// Builds the code image of rows [begin, end): code[i] = (C)(value[i] - base).
-// Whole 16-byte groups of values from the first row that is a multiple of 16
-// (so the packed stores stay aligned), the rows before and after one by one.
-template <typename T, typename C>
-__global__ __launch_bounds__(256) void scan_encode_kernel(const T *__restrict__ v, C *__restrict__ code, int64_t begin,
-                                                          int64_t end, uint64_t base) {
-  constexpr int R = 16 / (int)sizeof(T);
-  typedef typename std::conditional<sizeof(C) * R == 2, uint16_t, uint32_t>::type Out;
-  static_assert(sizeof(C) * R == sizeof(Out), "one packed store per 16-byte load");
-  int64_t a = (begin + 15) & ~(int64_t)15;
-  if (a > end) a = end;
-  const int64_t nvec = (end - a) / R;
-  const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (int64_t)gridDim.x * blockDim.x;
-  const v4i32 *src = (const v4i32 *)(v + a);
-  Out *dst = (Out *)(code + a);
-  auto pack = [&](v4i32 x) -> Out {
-    if (sizeof(T) == 8) {
-      const uint64_t c0 = ((uint64_t)(uint32_t)x.x | ((uint64_t)(uint32_t)x.y << 32)) - base;
-      const uint64_t c1 = ((uint64_t)(uint32_t)x.z | ((uint64_t)(uint32_t)x.w << 32)) - base;
-      return (Out)((uint32_t)(C)c0 | ((uint32_t)(C)c1 << (8 * sizeof(C))));
+// Builds the words of the code image that hold rows [begin, end): every word
+// from begin / F on is made whole from the values (the fields of rows >= end
+// stay zero), so extending an image never reads it back.  A block takes tiles
+// of 512 words: the 512 F values come in as coalesced 16-byte loads, their
+// codes go to LDS, and each thread packs two words from F neighbouring codes
+// and stores them, so no two threads ever write the same word.  The words
+// before the first tile (it starts at a word that is a multiple of 4, which
+// keeps the 16-byte loads aligned for every F) and after the last are packed
+// one per thread straight from the values.
+template <typename T, int F>
+__global__ __launch_bounds__(256) void scan_encode_kernel(const T *__restrict__ v, uint32_t *__restrict__ words,
+                                                          int64_t begin, int64_t end, uint64_t base) {
+  constexpr int BF = ScanFieldBits(F);
+  constexpr int R = 16 / (int)sizeof(T);  // rows per 16-byte load
+  constexpr int TW = 512;                 // words per tile
+  constexpr int UNITS = TW * F / R;       // 16-byte loads per tile
+  __shared__ __attribute__((aligned(16))) uint16_t lds[TW * F];
+  const int64_t w0 = begin / F, wend = ScanCodeWords(F, end), wfull = end / F;
+  int64_t wa = (w0 + 3) & ~(int64_t)3;
+  if (wa > wfull) wa = wfull;
+  const int64_t ntiles = (wfull - wa) / TW;
+  for (int64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+    const v4i32 *src = (const v4i32 *)(v + (wa + t * TW) * F);
+#pragma unroll 4
+    for (int u = threadIdx.x; u < UNITS; u += 256) {
+      const v4i32 x = __builtin_nontemporal_load(src + u);
+      if (sizeof(T) == 8) {
+        const uint64_t c0 = ((uint64_t)(uint32_t)x.x | ((uint64_t)(uint32_t)x.y << 32)) - base;
+        const uint64_t c1 = ((uint64_t)(uint32_t)x.z | ((uint64_t)(uint32_t)x.w << 32)) - base;
+        ((uint32_t *)lds)[u] = (uint32_t)(uint16_t)c0 | ((uint32_t)(uint16_t)c1 << 16);
+      } else {
+        const uint32_t c0 = (uint16_t)((uint64_t)(int64_t)x.x - base), c1 = (uint16_t)((uint64_t)(int64_t)x.y - base);
+        const uint32_t c2 = (uint16_t)((uint64_t)(int64_t)x.z - base), c3 = (uint16_t)((uint64_t)(int64_t)x.w - base);
+        ((uint2 *)lds)[u] = make_uint2(c0 | (c1 << 16), c2 | (c3 << 16));
+      }
     }
-    uint32_t o = 0;
-    const int xs[4] = {x.x, x.y, x.z, x.w};
+    __syncthreads();
 #pragma unroll
-    for (int e = 0; e < 4; e++) o |= (uint32_t)(C)((uint64_t)(int64_t)xs[e] - base) << (8 * sizeof(C) * e);
-    return (Out)o;
-  };
-  int64_t i = tid;
-  for (; i + 3 * stride < nvec; i += 4 * stride) {
-    const v4i32 x0 = __builtin_nontemporal_load(src + i), x1 = __builtin_nontemporal_load(src + i + stride);
-    const v4i32 x2 = __builtin_nontemporal_load(src + i + 2 * stride), x3 = __builtin_nontemporal_load(src + i + 3 * stride);
-    dst[i] = pack(x0);
-    dst[i + stride] = pack(x1);
-    dst[i + 2 * stride] = pack(x2);
-    dst[i + 3 * stride] = pack(x3);
+    for (int h = 0; h < TW / 256; h++) {
+      const int wi = h * 256 + threadIdx.x;
+      uint32_t o = 0;
+#pragma unroll
+      for (int e = 0; e < F; e++) o |= (uint32_t)lds[wi * F + e] << (BF * e);
+      words[wa + t * TW + wi] = o;
+    }
+    __syncthreads();
   }
-  for (; i < nvec; i += stride) dst[i] = pack(src[i]);
-  const int64_t nhead = a - begin, t0 = a + nvec * R, ntail = end - t0;
-  for (int64_t j = tid; j < nhead + ntail; j += stride) {
-    const int64_t row = j < nhead ? begin + j : t0 + (j - nhead);
-    code[row] = (C)((uint64_t)(int64_t)v[row] - base);
+  const int64_t nhead = wa - w0, t0 = wa + ntiles * TW, nslow = nhead + (wend - t0);
+  for (int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x; j < nslow; j += (int64_t)gridDim.x * 256) {
+    const int64_t wi = j < nhead ? w0 + j : t0 + (j - nhead);
+    uint32_t o = 0;
+#pragma unroll
+    for (int e = 0; e < F; e++) {
+      const int64_t row = wi * F + e;
+      if (row < end) o |= ((uint32_t)((uint64_t)(int64_t)v[row] - base) & ScanFieldMax(F)) << (BF * e);
+    }
+    words[wi] = o;
   }
 }
-
 // Multi-column version of the LDS-DMA filter-aggregate.  A wave step covers
 // 256 consecutive rows; each column's slice (1 KiB for int32, 2 KiB for
 // int64) lands in the wave's ring slot through global_load_lds; each lane
@@ -1125,42 +1164,65 @@ int FilterAggStates(const void *pcol, int pphys, int64_t lo, int64_t hi, bool ha
   return use_partials ? grid : 0;
 }
 
-int FilterAggCodes(const void *codes, int width, int64_t base, uint32_t clo, uint32_t cspan, bool packed, bool sum,
+template <int F>
+static void LaunchFilterAggCodes(const void *codes, int64_t base, uint32_t clo, uint32_t cspan, int form, bool sum,
+                                 int64_t nrows, AggPartial *partials, int grid, hipStream_t s) {
+#define FAC(MODE, FORM)                                                                                    \
+  hipLaunchKernelGGL((filter_agg_codes_kernel<F, MODE, 6, FORM>), dim3(grid), dim3(256), 0, s,              \
+                     (const uint32_t *)codes, nrows, clo, cspan, base, partials)
+#define FAC_M(MODE)                                \
+  switch (form) {                                  \
+    case SC_GUARD: FAC(MODE, SC_GUARD); break;     \
+    case SC_GE: FAC(MODE, SC_GE); break;           \
+    case SC_LE: FAC(MODE, SC_LE); break;           \
+    default: FAC(MODE, SC_BOTH); break;            \
+  }
+  if (!sum) { FAC_M(2) }
+  else if (form == SC_PER_CODE) FAC(0, SC_PER_CODE);
+  else { FAC_M(0) }
+#undef FAC_M
+#undef FAC
+}
+
+// Every field count ScanCodeFields can return.
+#define MBX_SCAN_FIELDS(X) X(32) X(16) X(10) X(8) X(6) X(5) X(4) X(3) X(2)
+
+int FilterAggCodes(const void *codes, int fields, int64_t base, uint32_t clo, uint32_t cspan, int form, bool sum,
                    bool need_minmax, int64_t nrows, AggPartial *partials, hipStream_t s) {
   int grid = NumCUs();
   if (grid > kMaxAggPartials) grid = kMaxAggPartials;
-  const int64_t pieces = nrows / (1024 / width) + 1;
+  const int64_t pieces = nrows / ScanPieceRows(fields) + 1;
   if ((int64_t)grid * 4 > pieces) grid = (int)((pieces + 3) / 4);
-#define FAC(W, MODE, MM, PK)                                                                                 \
-  hipLaunchKernelGGL((filter_agg_codes_kernel<W, MODE, 6, MM, PK>), dim3(grid), dim3(256), 0, s,              \
-                     (const unsigned char *)codes, nrows, clo, cspan, base, partials)
-#define FAC_W(W)                                                         \
-  if (!sum) { if (packed) FAC(W, 2, false, true); else FAC(W, 2, false, false); } \
-  else if (need_minmax) FAC(W, 0, true, false);                          \
-  else if (packed) FAC(W, 0, false, true);                               \
-  else FAC(W, 0, false, false)
-  if (width == 1) { FAC_W(1); }
-  else { FAC_W(2); }
-#undef FAC_W
-#undef FAC
+  if (sum && need_minmax) form = SC_PER_CODE;
+  switch (fields) {
+#define X(F) case F: LaunchFilterAggCodes<F>(codes, base, clo, cspan, form, sum, nrows, partials, grid, s); break;
+    MBX_SCAN_FIELDS(X)
+#undef X
+    default: throw std::runtime_error("FilterAggCodes: no kernel for " + std::to_string(fields) + " fields per word");
+  }
   CHECK_LAUNCH();
   return grid;
 }
 
-void ScanEncode(const void *values, int phys, void *codes, int width, int64_t base, int64_t begin, int64_t end,
+void ScanEncode(const void *values, int phys, void *codes, int fields, int64_t base, int64_t begin, int64_t end,
                 hipStream_t s) {
   if (end <= begin) return;
-  const int64_t units = (end - begin) / 16 + 1;  // a thread takes 4 16-byte groups per trip
-  const int grid = (int)std::min<int64_t>((units + 255) / 256, (int64_t)NumCUs() * 8);
-  if (phys == P_I64 && width == 1)
-    hipLaunchKernelGGL((scan_encode_kernel<int64_t, uint8_t>), dim3(grid), dim3(256), 0, s, (const int64_t *)values,
-                       (uint8_t *)codes, begin, end, (uint64_t)base);
-  else if (phys == P_I64)
-    hipLaunchKernelGGL((scan_encode_kernel<int64_t, uint16_t>), dim3(grid), dim3(256), 0, s, (const int64_t *)values,
-                       (uint16_t *)codes, begin, end, (uint64_t)base);
-  else
-    hipLaunchKernelGGL((scan_encode_kernel<int32_t, uint8_t>), dim3(grid), dim3(256), 0, s, (const int32_t *)values,
-                       (uint8_t *)codes, begin, end, (uint64_t)base);
+  const int64_t tiles = (end - begin) / (512 * (int64_t)fields) + 1;  // a block packs 512 words per trip
+  const int grid = (int)std::min<int64_t>(tiles, (int64_t)NumCUs() * 8);
+  switch (fields) {
+#define X(F)                                                                                                       \
+  case F:                                                                                                          \
+    if (phys == P_I64)                                                                                             \
+      hipLaunchKernelGGL((scan_encode_kernel<int64_t, F>), dim3(grid), dim3(256), 0, s, (const int64_t *)values,   \
+                         (uint32_t *)codes, begin, end, (uint64_t)base);                                           \
+    else                                                                                                           \
+      hipLaunchKernelGGL((scan_encode_kernel<int32_t, F>), dim3(grid), dim3(256), 0, s, (const int32_t *)values,   \
+                         (uint32_t *)codes, begin, end, (uint64_t)base);                                           \
+    break;
+    MBX_SCAN_FIELDS(X)
+#undef X
+    default: throw std::runtime_error("ScanEncode: no kernel for " + std::to_string(fields) + " fields per word");
+  }
   CHECK_LAUNCH();
 }
 
