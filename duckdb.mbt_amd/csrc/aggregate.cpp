@@ -729,6 +729,46 @@ static void PartGroupPrepare(Engine &e, const DRel &src, const PartGroupValues &
   d.scratch_scan_bytes = cb;
 }
 
+// The statement's WHERE as the passes take it (group_pred_plan.h): a
+// conjunction of integer range comparisons, planned against the zone maps of
+// this relation's columns.  keys: the key column(s) of the shape (code: they
+// fold into a group code).  false: not such a conjunction or the plan is Unfit
+// -- the path declines as it always did for a WHERE.
+static bool PartGroupPreds(const DRel &src, const BoundSelect &s, const std::vector<int> &keys, bool code,
+                           const PartGroupValues &v, GroupPredPlan &plan) {
+  plan = GroupPredPlan{};
+  plan.verdict = GroupPredVerdict::All;
+  if (!s.where) return true;
+  std::map<int, std::pair<i128, i128>> ranges;
+  if (!RangeConj(*s.where, ranges)) return false;
+  std::vector<GroupPredIn> in;
+  for (auto &kv : ranges) {
+    if (src.range && kv.first == 0) return false;
+    const DCol &c = src.cols[kv.first];
+    const DevColumn *tc = c.table_col;
+    GroupPredIn p = {};
+    p.col = kv.first;
+    p.data = c.data;
+    p.phys = c.phys;
+    p.has_validity = c.validity != nullptr;
+    p.stats_valid = tc && tc->stats_valid;
+    p.imin = tc ? tc->imin : 0;
+    p.imax = tc ? tc->imax : 0;
+    p.null_count = tc ? tc->null_count : 1;
+    p.lo = kv.second.first;
+    p.hi = kv.second.second;
+    in.push_back(p);
+  }
+  GroupPredShape shape = {};
+  shape.nkeys = (int)keys.size();
+  shape.code = code;
+  for (size_t i = 0; i < keys.size() && i < 4; i++) shape.key_cols[i] = keys[i];
+  shape.nv = (int)v.vcols.size();
+  for (size_t j = 0; j < v.vcols.size() && j < 2; j++) shape.val_cols[j] = v.vcols[j];
+  plan = PlanGroupPreds(in.data(), (int)in.size(), shape);
+  return plan.verdict != GroupPredVerdict::Unfit;
+}
+
 // algorithmic bytes of the value columns
 static double PartGroupValueBytes(const DRel &src, const PartGroupValues &v) {
   double bytes = 0;
@@ -804,12 +844,15 @@ static void PartGroupOneKeyOut(Engine &e, const BoundSelect &s, const PartGroupR
 // false: a table filled up (more groups than the tables hold) -- the caller's
 // hash path answers.
 static bool PartGroupHashedAggregate(Engine &e, const DRel &src, const BoundSelect &s, const DCol &K,
-                                     const PartGroupValues &v, DRel &out) {
+                                     const PartGroupValues &v, const GroupPredPlan &preds, DRel &out) {
   PartGroupRun r;
   PartGroupPrepare(e, src, v, 0, r);
   r.d.key = K.data;
   r.d.kphys = K.phys;
-  if (!PartGroupHashedRun(e, src, r, (double)src.n * PhysSize(K.phys) + PartGroupValueBytes(src, v))) return false;
+  r.d.pred = preds.set;
+  if (!PartGroupHashedRun(e, src, r,
+                          (double)src.n * (PhysSize(K.phys) + preds.own_bytes) + PartGroupValueBytes(src, v)))
+    return false;
   dev::EmitDesc D;
   memset(&D, 0, sizeof(D));
   D.key_msb = (const unsigned long long *)r.gk->p;
@@ -820,15 +863,18 @@ static bool PartGroupHashedAggregate(Engine &e, const DRel &src, const BoundSele
 
 // F3: GROUP BY one integer key (no NULLs) whose zone-map range is too wide for
 // F2's LDS tables but dense enough for per-key state arrays (1024 < range <=
-// PartGroupMaxRange, range <= 4 n), no WHERE, COUNT / SUM / MIN / MAX / AVG over
+// PartGroupMaxRange, range <= 4 n), COUNT / SUM / MIN / MAX / AVG over
 // <= 2 integer columns of one phys without NULLs: rows partitioned by key
 // range, each partition reduced in LDS (group_part.hip), then the non-empty
-// keys compacted and emitted in key order as F2 does.  false: the shape does
-// not fit (the hash path or the run-time compiled kernel takes it).
+// keys compacted and emitted in key order as F2 does.  A WHERE that is a
+// conjunction of integer range comparisons on up to GROUP_MAX_PRED columns
+// without NULLs is tested inside the hist and scatter passes (PartGroupPreds);
+// any other WHERE declines.  false: the shape does not fit (the hash path or
+// the run-time compiled kernel takes it).
 static bool PartGroupAggregate(Engine &e, const DRel &src, const BoundSelect &s, DRel &out) {
   if (const char *k = Knob("MBX_PART_GROUP"))  // MBX_PART_GROUP=0: the hash path (A/B)
     if (atoi(k) == 0) return false;
-  if (s.groups.size() != 1 || s.where || src.range || src.n <= 0 || src.n >= ((int64_t)1 << 32)) return false;
+  if (s.groups.size() != 1 || src.range || src.n <= 0 || src.n >= ((int64_t)1 << 32)) return false;
   if (s.groups[0]->kind != BExpr::COL || !FastIntCol(src, s.groups[0]->col)) return false;
   const DCol &K = src.cols[s.groups[0]->col];
   const DevColumn *ks = K.table_col;
@@ -836,20 +882,24 @@ static bool PartGroupAggregate(Engine &e, const DRel &src, const BoundSelect &s,
   const i128 range = ks->imax - ks->imin + 1;
   PartGroupValues v;
   if (!PartGroupValueCols(src, s, v) || range <= 1024) return false;
+  GroupPredPlan preds;
+  if (!PartGroupPreds(src, s, {s.groups[0]->col}, false, v, preds)) return false;
   const int nv = (int)v.vcols.size();
   // keys too sparse for dense per-key states: hashed partitions (F3h), from
   // 2^16 rows (below, the hash path's table is small) with at most one value column
   if (range > dev::PartGroupMaxRange(nv, v.mm) || range > 4 * (i128)src.n)
-    return nv <= 1 && src.n >= ((int64_t)1 << 16) && PartGroupHashedAggregate(e, src, s, K, v, out);
+    return nv <= 1 && src.n >= ((int64_t)1 << 16) && PartGroupHashedAggregate(e, src, s, K, v, preds, out);
   PartGroupRun r;
   PartGroupPrepare(e, src, v, (int64_t)range, r);
   r.d.key = K.data;
   r.d.kphys = K.phys;
   r.d.kmin = (int64_t)ks->imin;
   r.d.range = r.nslots;
+  r.d.pred = preds.set;
   {
-    // algorithmic bytes: the key and value columns once
-    ProfScope ps(e, "group_part", (double)src.n * PhysSize(K.phys) + PartGroupValueBytes(src, v), src.n);
+    // algorithmic bytes: the key, the value and the predicates' own columns once
+    ProfScope ps(e, "group_part",
+                 (double)src.n * (PhysSize(K.phys) + preds.own_bytes) + PartGroupValueBytes(src, v), src.n);
     if (!dev::PartGroup(r.d, e.stream)) return false;
   }
   dev::EmitDesc D;
@@ -862,7 +912,7 @@ static bool PartGroupAggregate(Engine &e, const DRel &src, const BoundSelect &s,
 
 // The same over the group code of 1..4 integer key columns and their validity
 // (group_code.h): GROUP BY k1, k2[, k3[, k4]], or one NULL-able key too wide
-// for F2's LDS tables.  No WHERE, at least 2^16 rows, more than 4096 codes (so
+// for F2's LDS tables.  A WHERE as F3 takes it, at least 2^16 rows, more than 4096 codes (so
 // the shape never competes with F2 or the run-time compiled jit_group); values
 // as F3 / F3h take them.  Dense codes (total <= PartGroupMaxRange and <= 4 n)
 // come out in code order -- key order, NULLs last per key, as F2 and jit_group
@@ -872,10 +922,11 @@ static bool CodeGroupAggregate(Engine &e, const DRel &src, const BoundSelect &s,
   const int ng = (int)s.groups.size();
   if (const char *k = Knob("MBX_PART_GROUP"))
     if (atoi(k) == 0) return false;
-  if (ng < 1 || ng > kGroupCodeMaxKeys || s.where || src.range || src.n < ((int64_t)1 << 16) ||
+  if (ng < 1 || ng > kGroupCodeMaxKeys || src.range || src.n < ((int64_t)1 << 16) ||
       src.n >= ((int64_t)1 << 32))
     return false;
   GroupCodeKeyIn in[kGroupCodeMaxKeys];
+  std::vector<int> kcols;
   bool nullable = false;
   for (int i = 0; i < ng; i++) {
     const BExpr *x = StripWidening(s.groups[i].get());
@@ -895,6 +946,7 @@ static bool CodeGroupAggregate(Engine &e, const DRel &src, const BoundSelect &s,
     in[i].imin = c.table_col->imin;
     in[i].imax = c.table_col->imax;
     nullable |= c.validity != nullptr;
+    kcols.push_back(x->col);
   }
   if (ng == 1 && !nullable) return false;  // F3's own shape
   GroupCodePlan plan;
@@ -904,13 +956,17 @@ static bool CodeGroupAggregate(Engine &e, const DRel &src, const BoundSelect &s,
   const int nv = (int)v.vcols.size();
   const bool dense = plan.total <= dev::PartGroupMaxRange(nv, v.mm) && (i128)plan.total <= 4 * (i128)src.n;
   if (!dense && nv > 1) return false;
-  // algorithmic bytes: every key column, n / 8 per validity bitmap, every value column
-  double bytes = PartGroupValueBytes(src, v);
+  GroupPredPlan preds;
+  if (!PartGroupPreds(src, s, kcols, true, v, preds)) return false;
+  // algorithmic bytes: every key column, n / 8 per validity bitmap, every value
+  // column, the predicates' own columns
+  double bytes = PartGroupValueBytes(src, v) + (double)src.n * preds.own_bytes;
   for (int i = 0; i < ng; i++)
     bytes += (double)src.n * PhysSize((Phys)in[i].phys) + (in[i].validity ? (double)src.n / 8 : 0);
   PartGroupRun r;
   PartGroupPrepare(e, src, v, dense ? plan.total : 0, r);
   r.d.code = &plan;
+  r.d.pred = preds.set;
   if (dense) {
     r.d.range = plan.total;
     ProfScope ps(e, "group_part", bytes, src.n);

@@ -6,6 +6,7 @@
 
 #include "group_code.h"
 #include "group_direct_plan.h"
+#include "group_pred_plan.h"
 #include "scan_codes.h"
 #include "str_match.h"
 #include "vm.h"
@@ -167,6 +168,11 @@ struct PartGroupDesc {
   // (group_code.h), computed in the hist and scatter passes; key / kphys are
   // unused, kmin = 0 and range = the plan's total on the dense path
   const GroupCodePlan *code;
+  // the statement's WHERE (group_pred_plan.h): pred.n > 0 entries are tested in
+  // the hist and scatter passes and only rows that pass become records;
+  // pred.empty: no row can pass and every key stays empty.  Scratch sizes stay
+  // those for n rows
+  GroupPredSet pred;
   const void *v0, *v1;
   int vphys, nv;
   bool mm;

@@ -28,7 +28,11 @@
 // HBM bytes per row with one INT64 key and value (c3h): 8 (hist) + 16 + 8
 // (scatter) + 8 (reduce) = 40 B against the 16 B the query names.  F3h (the
 // second half of this file) does the same over a hashed partition function
-// for keys too sparse for dense states.
+// for keys too sparse for dense states.  A WHERE that is a conjunction of
+// integer range predicates (group_pred_plan.h) is tested inside the hist and
+// scatter passes: rows that fail are not counted and never become records, and
+// start[np] holds the selected row count (c3h under x > 24, selectivity 0.52:
+// 16 + 24 + 8 x 0.52 + 8 x 0.52 = 48 B against 40).
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 #include <stdint.h>
@@ -39,6 +43,7 @@
 
 #include "device.h"
 #include "group_code.h"
+#include "group_pred_plan.h"
 #include "knobs.h"
 #include "phys.h"
 
@@ -87,14 +92,89 @@ struct PgCol {
   const TK *__restrict__ p;
   __device__ __forceinline__ int64_t operator()(int64_t r) const { return (int64_t)p[r]; }
 };
+
+// The WHERE of the statement (group_pred_plan.h): "has predicates" is the one
+// compile-time switch (PgNoPreds: the kernels as they were; PgPreds: their
+// *_pred siblings); the entries' count, widths and bounds are wave-uniform
+// fields of a struct passed by value.  A row's bit of the returned mask stays
+// set when it passes every entry.  An entry on the key or a value column is
+// compared in the register that load filled; one on a key column of a group
+// code is compared inside PgCode::rows.
+struct PgNoPreds {
+  static constexpr bool kOn = false;
+};
+struct PgPreds {
+  static constexpr bool kOn = true;
+  GroupPredSet s;
+  static __device__ __forceinline__ bool fails(const GroupPredEntry &E, int64_t x) {
+    return (uint64_t)x - (uint64_t)E.lo > E.span;
+  }
+  // Of N rows, the mask of those that pass ...
+  // ... every entry on a column of its own -- r(u): row u (in bounds).  Called
+  // before the rows' key and values are loaded, so the compared values and
+  // those never share registers (the 1024-thread kernels have 128 VGPRs).
+  // vals_loaded = false (the hist pass): an entry on a value column reads it here
+  template <int N, typename FR>
+  __device__ __forceinline__ uint32_t own(FR r, bool vals_loaded) const {
+    uint32_t m = (1u << N) - 1u;
+#pragma unroll
+    for (int j = 0; j < GROUP_MAX_PRED; j++) {
+      if (j >= s.n) break;  // (uniform, as every branch on an entry's fields)
+      const GroupPredEntry &E = s.p[j];
+      if (E.src != kPredOwn && (vals_loaded || (E.src != kPredV0 && E.src != kPredV1))) continue;
+      int64_t x[N];
+      if (E.phys == P_I64) {
+#pragma unroll
+        for (int u = 0; u < N; u++) x[u] = ((const int64_t *)E.data)[r(u)];
+      } else {
+#pragma unroll
+        for (int u = 0; u < N; u++) x[u] = (int64_t)((const int32_t *)E.data)[r(u)];
+      }
+#pragma unroll
+      for (int u = 0; u < N; u++)
+        if (fails(E, x[u])) m &= ~(1u << u);
+    }
+    return m;
+  }
+  // ... every entry on the key (single-key kernels: kv(u)) or on value column
+  // 0 / 1 (a(u) / c(u), where NV says the caller loaded them): compared in the
+  // registers those loads filled
+  template <int NV, int N, typename FK, typename FA, typename FC>
+  __device__ __forceinline__ uint32_t loaded(FK kv, FA a, FC c) const {
+    uint32_t m = (1u << N) - 1u;
+#pragma unroll
+    for (int j = 0; j < GROUP_MAX_PRED; j++) {
+      if (j >= s.n) break;
+      const GroupPredEntry &E = s.p[j];
+      if (E.src == kPredKey) {
+#pragma unroll
+        for (int u = 0; u < N; u++)
+          if (fails(E, kv(u))) m &= ~(1u << u);
+      } else if (NV >= 1 && E.src == kPredV0) {
+#pragma unroll
+        for (int u = 0; u < N; u++)
+          if (fails(E, (int64_t)a(u))) m &= ~(1u << u);
+      } else if (NV >= 2 && E.src == kPredV1) {
+#pragma unroll
+        for (int u = 0; u < N; u++)
+          if (fails(E, (int64_t)c(u))) m &= ~(1u << u);
+      }
+    }
+    return m;
+  }
+};
+
 struct PgCode {
   static constexpr bool kCode = true;
   GroupCodePlan plan;
   // codes of N rows, folded column by column (N loads of one column in flight,
   // then their multiply-adds), in A: uint32_t where total < 2^32 (the dense
-  // path: every digit x stride stays below total), else 64 bits
-  template <typename A, int N>
-  __device__ __forceinline__ void rows(const int64_t (&r)[N], A (&code)[N]) const {
+  // path: every digit x stride stays below total), else 64 bits.  With
+  // predicates, the entries on key column q clear the failing rows' bits of *keep
+  // (such a column has no NULLs: group_pred_plan.h).
+  template <typename A, int N, typename PR = PgNoPreds, typename R = int64_t>
+  __device__ __forceinline__ void rows(const R (&r)[N], A (&code)[N], const PR &pr = PR(),
+                                       uint32_t *keep = nullptr) const {
 #pragma unroll
     for (int u = 0; u < N; u++) code[u] = 0;
 #pragma unroll
@@ -102,7 +182,26 @@ struct PgCode {
       if (q >= plan.nkeys) break;  // (uniform)
       const GroupCodeKey &K = plan.k[q];
       A dg[N];
-      if (K.phys == P_I64) {
+      if constexpr (PR::kOn) {
+        int64_t x[N];
+        if (K.phys == P_I64) {
+#pragma unroll
+          for (int u = 0; u < N; u++) x[u] = ((const int64_t *)K.data)[r[u]];
+        } else {
+#pragma unroll
+          for (int u = 0; u < N; u++) x[u] = (int64_t)((const int32_t *)K.data)[r[u]];
+        }
+#pragma unroll
+        for (int j = 0; j < GROUP_MAX_PRED; j++) {
+          if (j >= pr.s.n) break;
+          if (pr.s.p[j].src != kPredCodeKey + q) continue;
+#pragma unroll
+          for (int u = 0; u < N; u++)
+            if (PR::fails(pr.s.p[j], x[u])) *keep &= ~(1u << u);
+        }
+#pragma unroll
+        for (int u = 0; u < N; u++) dg[u] = (A)((uint64_t)x[u] - (uint64_t)K.kmin);
+      } else if (K.phys == P_I64) {
 #pragma unroll
         for (int u = 0; u < N; u++) dg[u] = (A)((uint64_t)((const int64_t *)K.data)[r[u]] - (uint64_t)K.kmin);
       } else {
@@ -176,6 +275,62 @@ __global__ __launch_bounds__(1024) void pg_hist_code_kernel(const PgCode key, in
   for (int p = threadIdx.x; p < np; p += blockDim.x) hist[(size_t)p * gridDim.x + blockIdx.x] = h[p];
 }
 
+// ... and with the statement's WHERE (siblings again: the kernels above keep
+// their code): only rows that pass every entry are counted.  KS: PgCol<TK> or
+// PgCode (kmin = 0).
+template <bool HASHED, int N, typename KS>
+__device__ __forceinline__ void pg_hist_pred_rows(const KS &key, const PgPreds &pr, const uint32_t (&r)[N],
+                                                  int64_t kmin, int shift, unsigned int *h) {
+  int64_t kv[N];
+  uint32_t keep = pr.own<N>([&](int u) { return r[u]; }, false);  // (this pass loads no values)
+  if constexpr (KS::kCode) {
+    uint64_t c[N];
+    key.rows(r, c, pr, &keep);
+#pragma unroll
+    for (int u = 0; u < N; u++) kv[u] = (int64_t)c[u];
+  } else {
+#pragma unroll
+    for (int u = 0; u < N; u++) kv[u] = key(r[u]);
+  }
+  auto kvf = [&](int u) { return kv[u]; };
+  keep &= pr.loaded<0, N>(kvf, kvf, kvf);
+#pragma unroll
+  for (int u = 0; u < N; u++)
+    if ((keep >> u) & 1) atomicAdd(&h[pg_part<HASHED>(kv[u], kmin, shift)], 1u);
+}
+
+template <typename KS, bool HASHED>
+__global__ __launch_bounds__(1024) void pg_hist_pred_kernel(const KS key, const PgPreds pr, int64_t n, int64_t chunk,
+                                                           int64_t kmin, int shift, int np,
+                                                           unsigned int *__restrict__ hist /* [np][grid] */) {
+  extern __shared__ unsigned int h[];
+  for (int p = threadIdx.x; p < np; p += blockDim.x) h[p] = 0;
+  __syncthreads();
+  const int64_t b = (int64_t)blockIdx.x * chunk, e = min(n, b + chunk);
+  const int64_t B = blockDim.x;
+  int64_t i = b + threadIdx.x;
+  // four rows in flight per lane; n < 2^32: 32-bit row indices
+  constexpr int U = 4;
+  for (; i + (U - 1) * B < e; i += U * B) {
+    uint32_t r[U];
+#pragma unroll
+    for (int u = 0; u < U; u++) r[u] = (uint32_t)(i + u * B);
+    pg_hist_pred_rows<HASHED>(key, pr, r, kmin, shift, h);
+  }
+  for (; i < e; i += B) {
+    const uint32_t r[1] = {(uint32_t)i};
+    pg_hist_pred_rows<HASHED>(key, pr, r, kmin, shift, h);
+  }
+  __syncthreads();
+  for (int p = threadIdx.x; p < np; p += blockDim.x) hist[(size_t)p * gridDim.x + blockIdx.x] = h[p];
+}
+
+// start[np] = the number of selected rows: the last offset plus the last count
+__global__ void pg_total_kernel(const unsigned int *__restrict__ off, const unsigned int *__restrict__ hist, int nh,
+                                unsigned int *__restrict__ total) {
+  if (threadIdx.x == 0 && blockIdx.x == 0) *total = off[nh - 1] + hist[nh - 1];
+}
+
 // Rows of a workgroup's chunk in tiles of kTile: each tile is counting-sorted
 // by partition in LDS (a returning LDS add gives a row its rank in its
 // partition, a block scan the partitions' bases), staged there, and written
@@ -189,9 +344,9 @@ __global__ __launch_bounds__(1024) void pg_hist_code_kernel(const PgCode key, in
 // tiles in two 8-wave workgroups per CU (one stages while the other stores)
 constexpr int kScatterThreads = 512, kTile = 4096;
 
-template <typename TV, int NV, bool PACK, int TILE, typename KS>
+template <typename TV, int NV, bool PACK, int TILE, typename KS, typename PR>
 __device__ __forceinline__ void pg_scatter_body(
-    const KS &key, const TV *__restrict__ v0, const TV *__restrict__ v1, int64_t n, int64_t chunk,
+    const KS &key, const PR &pr, const TV *__restrict__ v0, const TV *__restrict__ v1, int64_t n, int64_t chunk,
     int64_t kmin, int shift, int np, const unsigned int *__restrict__ off /* [np][grid] */, uint16_t *__restrict__ ok,
     TV *__restrict__ ov0, TV *__restrict__ ov1) {
   constexpr int kTile = TILE, kScatterThreads = TILE / 8;
@@ -212,10 +367,40 @@ __device__ __forceinline__ void pg_scatter_body(
   // the next tile is loaded into registers while this one's rows are stored
   // (straight-line loads and stores, as in pg_hscatter: a row past the chunk
   // loads the chunk's last row and stores into the pad slot after each array)
+  // With predicates (PR::kOn) a rejected row is handled like a row past the
+  // chunk: loaded (every row's index is in bounds), never ranked and never
+  // staged, so a tile stages the sum of its partition counts instead of tn
+  // rows and the slots from there on are the pad slot's.
   uint32_t rel[RPT];
   TV a[RPT], c[RPT];
+  [[maybe_unused]] uint32_t keep = 0;  // PR::kOn: bit u = row u of the loaded tile passes
+  auto kept = [&](int u) {
+    if constexpr (PR::kOn) return ((keep >> u) & 1u) != 0;
+    else return true;
+  };
   auto load = [&](int64_t tb) {
-    if constexpr (KS::kCode) {  // (the validity loads follow the same clamp)
+    if constexpr (PR::kOn) {
+      // (n < 2^32 on every path here: a row index takes one register)
+      auto row = [&](int u) { return (uint32_t)min(tb + u * kScatterThreads + t, e - 1); };
+      keep = pr.template own<RPT>(row, true);
+      if constexpr (KS::kCode) {
+        uint32_t r[RPT];
+#pragma unroll
+        for (int u = 0; u < RPT; u++) r[u] = row(u);
+        key.rows(r, rel, pr, &keep);
+      } else {
+#pragma unroll
+        for (int u = 0; u < RPT; u++) rel[u] = (uint32_t)(key(row(u)) - kmin);
+      }
+#pragma unroll
+      for (int u = 0; u < RPT; u++) {
+        if (NV >= 1) a[u] = v0[row(u)];
+        if (NV >= 2) c[u] = v1[row(u)];
+      }
+      // (a key lies in its zone map, so key - kmin fits rel; no kPredKey entry with a group code)
+      keep &= pr.template loaded<NV, RPT>([&](int u) { return kmin + (int64_t)rel[u]; }, [&](int u) { return a[u]; },
+                                          [&](int u) { return c[u]; });
+    } else if constexpr (KS::kCode) {  // (the validity loads follow the same clamp)
       int64_t r[RPT];
 #pragma unroll
       for (int u = 0; u < RPT; u++) r[u] = min(tb + u * kScatterThreads + t, e - 1);
@@ -244,7 +429,7 @@ __device__ __forceinline__ void pg_scatter_body(
     auto row_of = [&](int u) { return u * kScatterThreads + t; };
 #pragma unroll
     for (int u = 0; u < RPT; u++)
-      if (row_of(u) < tn) rank[u] = atomicAdd(&cnt[rel[u] >> shift], 1u);
+      if (row_of(u) < tn && kept(u)) rank[u] = atomicAdd(&cnt[rel[u] >> shift], 1u);
     __syncthreads();
     // exclusive scan of cnt[0, np): each thread a run of consecutive entries,
     // then the runs' totals across the block
@@ -266,9 +451,12 @@ __device__ __forceinline__ void pg_scatter_body(
       before += cnt[p];
     }
     __syncthreads();
+    // rows staged by this tile: every row of it, or with predicates those that passed
+    int sn = tn;
+    if constexpr (PR::kOn) sn = __builtin_amdgcn_readfirstlane((int)(base[np - 1] + cnt[np - 1]));  // (uniform)
 #pragma unroll
     for (int u = 0; u < RPT; u++) {
-      if (row_of(u) >= tn) continue;
+      if (row_of(u) >= tn || !kept(u)) continue;
       const int pp = (int)(rel[u] >> shift);
       const unsigned int pos = base[pp] + rank[u];
       sp[pos] = (uint16_t)pp;
@@ -285,9 +473,9 @@ __device__ __forceinline__ void pg_scatter_body(
 #pragma unroll
     for (int u = 0; u < RPT; u++) {
       const int j = u * kScatterThreads + t;
-      const int jj = min(j, tn - 1);
-      const int pp = sp[jj];
-      const size_t dst = j < tn ? (size_t)(cur[pp] + (unsigned int)j - base[pp]) : (size_t)n;  // (n: the pad slot)
+      const int jj = PR::kOn ? max(min(j, sn - 1), 0) : min(j, tn - 1);  // (sn may be 0)
+      const int pp = PR::kOn && j >= sn ? 0 : sp[jj];
+      const size_t dst = j < sn ? (size_t)(cur[pp] + (unsigned int)j - base[pp]) : (size_t)n;  // (n: the pad slot)
       if (!PACK) ok[dst] = sk[jj];
       if (NV >= 1) ov0[dst] = sv0[jj];
       if (NV >= 2) ov1[dst] = sv1[jj];
@@ -302,14 +490,23 @@ __global__ __launch_bounds__(TILE / 8) void pg_scatter_kernel(
     const TK *__restrict__ key, const TV *__restrict__ v0, const TV *__restrict__ v1, int64_t n, int64_t chunk,
     int64_t kmin, int shift, int np, const unsigned int *__restrict__ off /* [np][grid] */, uint16_t *__restrict__ ok,
     TV *__restrict__ ov0, TV *__restrict__ ov1) {
-  pg_scatter_body<TV, NV, PACK, TILE>(PgCol<TK>{key}, v0, v1, n, chunk, kmin, shift, np, off, ok, ov0, ov1);
+  pg_scatter_body<TV, NV, PACK, TILE>(PgCol<TK>{key}, PgNoPreds(), v0, v1, n, chunk, kmin, shift, np, off, ok, ov0,
+                                      ov1);
 }
 template <typename TV, int NV, bool PACK, int TILE>
 __global__ __launch_bounds__(TILE / 8) void pg_scatter_code_kernel(
     const PgCode key, const TV *__restrict__ v0, const TV *__restrict__ v1, int64_t n, int64_t chunk, int shift,
     int np, const unsigned int *__restrict__ off, uint16_t *__restrict__ ok, TV *__restrict__ ov0,
     TV *__restrict__ ov1) {
-  pg_scatter_body<TV, NV, PACK, TILE>(key, v0, v1, n, chunk, (int64_t)0, shift, np, off, ok, ov0, ov1);
+  pg_scatter_body<TV, NV, PACK, TILE>(key, PgNoPreds(), v0, v1, n, chunk, (int64_t)0, shift, np, off, ok, ov0, ov1);
+}
+// ... with the statement's WHERE, over either key source (PgCode: kmin = 0)
+template <typename KS, typename TV, int NV, bool PACK, int TILE>
+__global__ __launch_bounds__(TILE / 8) void pg_scatter_pred_kernel(
+    const KS key, const PgPreds pr, const TV *__restrict__ v0, const TV *__restrict__ v1, int64_t n, int64_t chunk,
+    int64_t kmin, int shift, int np, const unsigned int *__restrict__ off, uint16_t *__restrict__ ok,
+    TV *__restrict__ ov0, TV *__restrict__ ov1) {
+  pg_scatter_body<TV, NV, PACK, TILE>(key, pr, v0, v1, n, chunk, kmin, shift, np, off, ok, ov0, ov1);
 }
 
 // the reduce passes' piece: at most 2^20 rows, and the piece count a multiple
@@ -340,7 +537,8 @@ __device__ __forceinline__ void pc_split(unsigned long long w, unsigned int *c, 
 }
 
 // Piece q = rows [q * piece, min(n, (q + 1) * piece)) of the partitioned
-// arrays; start[p] = first row of partition p (start[np] = n).  LDS: the
+// arrays; start[p] = first row of partition p (start[np] = n, or under
+// predicates the selected row count: pieces past it find nothing).  LDS: the
 // partition's table of KP keys -- COUNT(*) u32, then per value column its int64
 // sum (and min / max).
 template <typename TV, int NV, bool MM, bool PACK, bool PC>
@@ -472,11 +670,11 @@ constexpr int kHashSlots = 4096;   // LDS table of a piece
 constexpr int kHashGlobal = 8192;  // global table per partition
 constexpr uint64_t kMsb = 0x8000000000000000ull;
 
-template <typename TV, int NV, typename KS>
+template <typename TV, int NV, int TILE, typename KS, typename PR>
 __device__ __forceinline__ void pg_hscatter_body(
-    const KS &key, const TV *__restrict__ v0, int64_t n, int64_t chunk, int pbits, int np,
+    const KS &key, const PR &pr, const TV *__restrict__ v0, int64_t n, int64_t chunk, int pbits, int np,
     const unsigned int *__restrict__ off, int64_t *__restrict__ rec /* [n][NV + 1] */) {
-  constexpr int kTile = kHTile, kScatterThreads = kHThreads;
+  constexpr int kTile = TILE, kScatterThreads = kHThreads;
   constexpr int RPT = kTile / kScatterThreads, RS = NV + 1;
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   int64_t *srec = (int64_t *)lds;                                   // staged records
@@ -492,9 +690,36 @@ __device__ __forceinline__ void pg_hscatter_body(
   // wait for the prefetched rows counts past the stores issued after them
   // instead of draining them: a row past the chunk loads the chunk's last row
   // and stores into the pad slot after the records.
+  // (predicates: as in pg_scatter_body)
   int64_t kk[RPT], vv[RPT];
+  [[maybe_unused]] uint32_t keep = 0;
+  auto kept = [&](int u) {
+    if constexpr (PR::kOn) return ((keep >> u) & 1u) != 0;
+    else return true;
+  };
   auto load = [&](int64_t tb) {
-    if constexpr (KS::kCode) {
+    if constexpr (PR::kOn) {
+      // (n < 2^32 on every path here: a row index takes one register)
+      auto row = [&](int u) { return (uint32_t)min(tb + u * kScatterThreads + t, e - 1); };
+      keep = pr.template own<RPT>(row, true);
+      if constexpr (KS::kCode) {
+        uint32_t r[RPT];
+#pragma unroll
+        for (int u = 0; u < RPT; u++) r[u] = row(u);
+        uint64_t code[RPT];
+        key.rows(r, code, pr, &keep);
+#pragma unroll
+        for (int u = 0; u < RPT; u++) kk[u] = (int64_t)code[u];
+      } else {
+#pragma unroll
+        for (int u = 0; u < RPT; u++) kk[u] = key(row(u));
+      }
+#pragma unroll
+      for (int u = 0; u < RPT; u++)
+        if (NV >= 1) vv[u] = (int64_t)v0[row(u)];
+      auto vf = [&](int u) { return vv[u]; };
+      keep &= pr.template loaded<NV, RPT>([&](int u) { return kk[u]; }, vf, vf);
+    } else if constexpr (KS::kCode) {
       int64_t r[RPT];
 #pragma unroll
       for (int u = 0; u < RPT; u++) r[u] = min(tb + u * kScatterThreads + t, e - 1);
@@ -526,7 +751,7 @@ __device__ __forceinline__ void pg_hscatter_body(
       if (u * kScatterThreads + t < tn) pp[u] = pg_part<true>(kk[u], 0, pbits);
 #pragma unroll
     for (int u = 0; u < RPT; u++)
-      if (u * kScatterThreads + t < tn) rank[u] = atomicAdd(&cnt[pp[u]], 1u);
+      if (u * kScatterThreads + t < tn && kept(u)) rank[u] = atomicAdd(&cnt[pp[u]], 1u);
     __syncthreads();
     const int per = (np + kScatterThreads - 1) / kScatterThreads, p0 = min(np, t * per), p1 = min(np, p0 + per);
     unsigned int run = 0;
@@ -546,9 +771,11 @@ __device__ __forceinline__ void pg_hscatter_body(
       before += cnt[p];
     }
     __syncthreads();
+    int sn = tn;  // rows staged by this tile
+    if constexpr (PR::kOn) sn = __builtin_amdgcn_readfirstlane((int)(base[np - 1] + cnt[np - 1]));  // (uniform)
 #pragma unroll
     for (int u = 0; u < RPT; u++) {
-      if (u * kScatterThreads + t >= tn) continue;
+      if (u * kScatterThreads + t >= tn || !kept(u)) continue;
       const unsigned int pos = base[pp[u]] + rank[u];
       sp[pos] = (uint16_t)pp[u];
       srec[(size_t)pos * RS] = (int64_t)((uint64_t)kk[u] ^ kMsb);
@@ -559,9 +786,9 @@ __device__ __forceinline__ void pg_hscatter_body(
 #pragma unroll
     for (int u = 0; u < RPT; u++) {
       const int j = u * kScatterThreads + t;
-      const int jj = min(j, tn - 1);
-      const int q = sp[jj];
-      const size_t dst = j < tn ? (size_t)(cur[q] + (unsigned int)j - base[q]) : (size_t)n;  // (n: the pad slot)
+      const int jj = PR::kOn ? max(min(j, sn - 1), 0) : min(j, tn - 1);  // (sn may be 0)
+      const int q = PR::kOn && j >= sn ? 0 : sp[jj];
+      const size_t dst = j < sn ? (size_t)(cur[q] + (unsigned int)j - base[q]) : (size_t)n;  // (n: the pad slot)
       if (NV >= 1) {
         typedef int64_t P __attribute__((ext_vector_type(2)));
         *(P *)(rec + dst * 2) = *(const P *)(srec + (size_t)jj * 2);
@@ -578,14 +805,25 @@ template <typename TK, typename TV, int NV>
 __global__ __launch_bounds__(kHThreads) void pg_hscatter_kernel(
     const TK *__restrict__ key, const TV *__restrict__ v0, int64_t n, int64_t chunk, int pbits, int np,
     const unsigned int *__restrict__ off, int64_t *__restrict__ rec /* [n][NV + 1] */) {
-  pg_hscatter_body<TV, NV>(PgCol<TK>{key}, v0, n, chunk, pbits, np, off, rec);
+  pg_hscatter_body<TV, NV, kHTile>(PgCol<TK>{key}, PgNoPreds(), v0, n, chunk, pbits, np, off, rec);
 }
 // (codes are >= 0: code ^ 2^63 is never 0, the INT64_MIN slot stays unused)
 template <typename TV, int NV>
 __global__ __launch_bounds__(kHThreads) void pg_hscatter_code_kernel(
     const PgCode key, const TV *__restrict__ v0, int64_t n, int64_t chunk, int pbits, int np,
     const unsigned int *__restrict__ off, int64_t *__restrict__ rec) {
-  pg_hscatter_body<TV, NV>(key, v0, n, chunk, pbits, np, off, rec);
+  pg_hscatter_body<TV, NV, kHTile>(key, PgNoPreds(), v0, n, chunk, pbits, np, off, rec);
+}
+// Over a group code with predicates the 8192-row tile's eight rows per thread
+// do not fit 128 VGPRs beside the plan's and the entries' fields (2-4 dwords of
+// scratch): that one shape takes 4096-row tiles, four rows per thread.
+template <typename KS>
+constexpr int kHPredTile = KS::kCode ? kHTile / 2 : kHTile;
+template <typename KS, typename TV, int NV>
+__global__ __launch_bounds__(kHThreads) void pg_hscatter_pred_kernel(
+    const KS key, const PgPreds pr, const TV *__restrict__ v0, int64_t n, int64_t chunk, int pbits, int np,
+    const unsigned int *__restrict__ off, int64_t *__restrict__ rec) {
+  pg_hscatter_body<TV, NV, kHPredTile<KS>>(key, pr, v0, n, chunk, pbits, np, off, rec);
 }
 
 template <int NV, bool MM, bool PC>
@@ -742,7 +980,26 @@ bool PartGroupHashed(const PartGroupDesc &d, unsigned long long *gkeys, int *ove
   const size_t hl = (size_t)np * 4;
   PgCode code;
   if (d.code) code.plan = *d.code;
-  if (d.code)
+  const bool pred = d.pred.n > 0;
+  PgPreds pr;
+  pr.s = d.pred;
+  const int64_t total = (int64_t)np * kHashGlobal + 1;
+  if (d.pred.empty) {  // no row can pass: every table stays empty
+    (void)hipMemsetAsync(gkeys, 0, (size_t)total * 8, s);
+    (void)hipMemsetAsync(overflow, 0, 4, s);
+    InitAggStatesCounts(d.st0, total, d.cstar, total, s);
+    return hipGetLastError() == hipSuccess;
+  }
+  const PgCol<int64_t> k64{(const int64_t *)d.key};
+  const PgCol<int32_t> k32{(const int32_t *)d.key};
+#define PHH(KS, K)                                                                                                  \
+  hipLaunchKernelGGL((pg_hist_pred_kernel<KS, true>), dim3(grid), dim3(kHThreads), hl, s, K, pr, d.n, chunk,        \
+                     (int64_t)0, pbits, np, hist)
+  if (pred) {
+    if (d.code) PHH(PgCode, code);
+    else if (d.kphys == P_I64) PHH(PgCol<int64_t>, k64);
+    else PHH(PgCol<int32_t>, k32);
+  } else if (d.code)
     hipLaunchKernelGGL((pg_hist_code_kernel<true>), dim3(grid), dim3(kHThreads), hl, s, code, d.n, chunk, pbits, np,
                        hist);
   else if (d.kphys == P_I64)
@@ -756,9 +1013,13 @@ bool PartGroupHashed(const PartGroupDesc &d, unsigned long long *gkeys, int *ove
   (void)hipcub::DeviceScan::ExclusiveSum(nullptr, tmp, hist, off, nh, s);
   if (tmp > d.scratch_scan_bytes) throw std::runtime_error("PartGroupHashed: scan scratch too small");
   (void)hipcub::DeviceScan::ExclusiveSum(d.scratch_scan, tmp, hist, off, nh, s);
+#undef PHH
   (void)hipMemcpy2DAsync(start, 4, off, (size_t)grid * 4, 4, np, hipMemcpyDeviceToDevice, s);
-  (void)hipMemsetD32Async((hipDeviceptr_t)(start + np), (int)(unsigned int)d.n, 1, s);
-  const size_t sl = (size_t)kHTile * 8 * (d.nv + 1) + (size_t)kHTile * 2 + (size_t)np * 12 + 64;
+  // start[np]: the rows that became records -- n, or with predicates the scan's total
+  if (pred) hipLaunchKernelGGL(pg_total_kernel, dim3(1), dim3(64), 0, s, off, hist, nh, start + np);
+  else (void)hipMemsetD32Async((hipDeviceptr_t)(start + np), (int)(unsigned int)d.n, 1, s);
+  const int htile = pred && d.code ? kHPredTile<PgCode> : kHTile;
+  const size_t sl = (size_t)htile * 8 * (d.nv + 1) + (size_t)htile * 2 + (size_t)np * 12 + 64;
 #define PHS(TK, TV, NV)                                                                                             \
   {                                                                                                                 \
     (void)hipFuncSetAttribute((const void *)pg_hscatter_kernel<TK, TV, NV>,                                         \
@@ -777,15 +1038,29 @@ bool PartGroupHashed(const PartGroupDesc &d, unsigned long long *gkeys, int *ove
     hipLaunchKernelGGL((pg_hscatter_code_kernel<TV, NV>), dim3(grid), dim3(kHThreads), sl, s, code,                 \
                        (const TV *)d.v0, d.n, chunk, pbits, np, off, rec);                                          \
   }
-  if (d.code) {
+#define PHP(KS, K, TV, NV)                                                                                          \
+  {                                                                                                                 \
+    (void)hipFuncSetAttribute((const void *)pg_hscatter_pred_kernel<KS, TV, NV>,                                    \
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)sl);                                 \
+    hipLaunchKernelGGL((pg_hscatter_pred_kernel<KS, TV, NV>), dim3(grid), dim3(kHThreads), sl, s, K, pr,           \
+                       (const TV *)d.v0, d.n, chunk, pbits, np, off, rec);                                          \
+  }
+#define PHPV(KS, K)                                                                                                 \
+  if (d.nv == 0) PHP(KS, K, int64_t, 0)                                                                             \
+  else if (d.vphys == P_I64) PHP(KS, K, int64_t, 1)                                                                 \
+  else PHP(KS, K, int32_t, 1)
+  if (pred) {
+    if (d.code) { PHPV(PgCode, code) } else if (d.kphys == P_I64) { PHPV(PgCol<int64_t>, k64) } else { PHPV(PgCol<int32_t>, k32) }
+  } else if (d.code) {
     if (d.nv == 0) PHSC(int64_t, 0)
     else if (d.vphys == P_I64) PHSC(int64_t, 1)
     else PHSC(int32_t, 1)
   } else if (d.kphys == P_I64) { PHSV(int64_t) } else { PHSV(int32_t) }
+#undef PHPV
+#undef PHP
 #undef PHSC
 #undef PHSV
 #undef PHS
-  const int64_t total = (int64_t)np * kHashGlobal + 1;
   (void)hipMemsetAsync(gkeys, 0, (size_t)total * 8, s);
   (void)hipMemsetAsync(overflow, 0, 4, s);
   InitAggStatesCounts(d.st0, total, d.cstar, total, s);
@@ -872,7 +1147,23 @@ bool PartGroup(const PartGroupDesc &d, hipStream_t s) {
   const size_t hl = (size_t)np * 4;
   PgCode code;
   if (d.code) code.plan = *d.code;
-  if (d.code)
+  const bool pred = d.pred.n > 0;
+  PgPreds pr;
+  pr.s = d.pred;
+  if (d.pred.empty) {  // no row can pass: every key stays empty
+    InitAggStatesCounts(d.st0, d.nv >= 2 ? 2 * d.range : d.range, d.cstar, d.range, s);
+    return hipGetLastError() == hipSuccess;
+  }
+  const PgCol<int64_t> k64{(const int64_t *)d.key};
+  const PgCol<int32_t> k32{(const int32_t *)d.key};
+#define PGH(KS, K)                                                                                                  \
+  hipLaunchKernelGGL((pg_hist_pred_kernel<KS, false>), dim3(grid), dim3(sthreads), hl, s, K, pr, d.n, chunk,        \
+                     d.kmin, shift, np, hist)
+  if (pred) {
+    if (d.code) PGH(PgCode, code);
+    else if (d.kphys == P_I64) PGH(PgCol<int64_t>, k64);
+    else PGH(PgCol<int32_t>, k32);
+  } else if (d.code)
     hipLaunchKernelGGL(pg_hist_code_kernel<false>, dim3(grid), dim3(sthreads), hl, s, code, d.n, chunk, shift, np,
                        hist);
   else if (d.kphys == P_I64)
@@ -888,8 +1179,12 @@ bool PartGroup(const PartGroupDesc &d, hipStream_t s) {
   (void)hipcub::DeviceScan::ExclusiveSum(nullptr, tmp, hist, off, nh, s);
   if (tmp > d.scratch_scan_bytes) throw std::runtime_error("PartGroup: scan scratch too small");
   (void)hipcub::DeviceScan::ExclusiveSum(d.scratch_scan, tmp, hist, off, nh, s);
+#undef PGH
   (void)hipMemcpy2DAsync(start, 4, off, (size_t)grid * 4, 4, np, hipMemcpyDeviceToDevice, s);
-  (void)hipMemsetD32Async((hipDeviceptr_t)(start + np), (int)(unsigned int)d.n, 1, s);
+  // start[np]: the rows that became records -- n, or with predicates the scan's
+  // total m (a reduce piece past m finds its partitions clipped to nothing)
+  if (pred) hipLaunchKernelGGL(pg_total_kernel, dim3(1), dim3(64), 0, s, off, hist, nh, start + np);
+  else (void)hipMemsetD32Async((hipDeviceptr_t)(start + np), (int)(unsigned int)d.n, 1, s);
 #define PGS1(TK, TV, NV, PK, T)                                                                                     \
   {                                                                                                                 \
     (void)hipFuncSetAttribute((const void *)pg_scatter_kernel<TK, TV, NV, PK, T>,                                   \
@@ -920,7 +1215,30 @@ bool PartGroup(const PartGroupDesc &d, hipStream_t s) {
   }
 #define PGC(TV, NV, PK)                                                                                             \
   if (tile == 8192) PGC1(TV, NV, PK, 8192) else PGC1(TV, NV, PK, 4096)
-  if (d.code) {
+// ... and with predicates, over either key source
+#define PGP1(KS, K, TV, NV, PK, T)                                                                                  \
+  {                                                                                                                 \
+    (void)hipFuncSetAttribute((const void *)pg_scatter_pred_kernel<KS, TV, NV, PK, T>,                              \
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)sl);                                 \
+    hipLaunchKernelGGL((pg_scatter_pred_kernel<KS, TV, NV, PK, T>), dim3(grid), dim3(T / 8), sl, s, K, pr,          \
+                       (const TV *)d.v0, (const TV *)d.v1, d.n, chunk, d.kmin, shift, np, off, rk, (TV *)rv0,       \
+                       (TV *)rv1);                                                                                  \
+  }
+#define PGP(KS, K, TV, NV, PK)                                                                                      \
+  if (tile == 8192) PGP1(KS, K, TV, NV, PK, 8192) else PGP1(KS, K, TV, NV, PK, 4096)
+#define PGPV(KS, K)                                                                                                 \
+  if (d.vphys == P_I64) {                                                                                           \
+    if (d.nv == 0) PGP(KS, K, int64_t, 0, false)                                                                    \
+    else if (d.nv == 1) { if (pack) PGP(KS, K, int64_t, 1, true) else PGP(KS, K, int64_t, 1, false) }               \
+    else PGP(KS, K, int64_t, 2, false)                                                                              \
+  } else {                                                                                                          \
+    if (d.nv == 0) PGP(KS, K, int32_t, 0, false)                                                                    \
+    else if (d.nv == 1) PGP(KS, K, int32_t, 1, false)                                                               \
+    else PGP(KS, K, int32_t, 2, false)                                                                              \
+  }
+  if (pred) {
+    if (d.code) { PGPV(PgCode, code) } else if (d.kphys == P_I64) { PGPV(PgCol<int64_t>, k64) } else { PGPV(PgCol<int32_t>, k32) }
+  } else if (d.code) {
     if (d.vphys == P_I64) {
       if (d.nv == 0) PGC(int64_t, 0, false)
       else if (d.nv == 1) { if (pack) PGC(int64_t, 1, true) else PGC(int64_t, 1, false) }
@@ -931,6 +1249,9 @@ bool PartGroup(const PartGroupDesc &d, hipStream_t s) {
       else PGC(int32_t, 2, false)
     }
   } else if (d.kphys == P_I64) { PGSV(int64_t) } else { PGSV(int32_t) }
+#undef PGPV
+#undef PGP
+#undef PGP1
 #undef PGC
 #undef PGC1
 #undef PGSV
