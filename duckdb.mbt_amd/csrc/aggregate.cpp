@@ -1042,7 +1042,25 @@ static bool ScanAggregate(Engine &e, const DRel &src, const BoundSelect &s, DRel
                           (!A || A == P) && src.n < ((int64_t)1 << 40);
     bool need_mm = false;
     for (auto &a : s.aggs) need_mm |= a.kind == A_MIN || a.kind == A_MAX;
-    if (by_codes) {
+    auto known_count = [&]() {  // every row passes and only their number is asked
+      dev::InitAggStatesCounts(st, 1, cstar, 1, e.stream);
+      unsigned long long c = (unsigned long long)src.n;
+      HIPCHK(hipMemcpyAsync(cstar, &c, 8, hipMemcpyHostToDevice, e.stream));
+      HIPCHK(hipStreamSynchronize(e.stream));
+    };
+    if (by_codes && tc->code_planes > 0) {
+      const ScanPlanePlan pp =
+          PlanScanPlanes(tc->code_planes, (i128)tc->code_base, tc->imax, (int64_t)lo, (int64_t)hi, A != nullptr);
+      ProfScope ps(e, "filter_agg", pp.empty ? 0 : (double)ScanPlaneScanBytes(pp.planes, src.n), src.n);
+      if (pp.empty) {
+        dev::InitAggStatesCounts(st, 1, cstar, 1, e.stream);  // the zone map rules every row out, as below
+      } else if (pp.planes == 0) {
+        known_count();  // it lets every row in: no plane is read
+      } else {
+        npartials = dev::FilterAggPlanes(tc->codes, tc->code_planes, pp.planes, pp.ge, pp.le, pp.clo, pp.chi,
+                                         tc->code_base, A != nullptr, need_mm, src.n, e.d_partials, e.stream);
+      }
+    } else if (by_codes) {
       const ScanCodeRange cr = PlanScanFieldRange(tc->code_fields, (i128)tc->code_base, tc->imax, (int64_t)lo, (int64_t)hi);
       if (cr.empty) {
         // the zone map rules every row out: no scan (the entry keeps the
@@ -1070,10 +1088,7 @@ static bool ScanAggregate(Engine &e, const DRel &src, const BoundSelect &s, DRel
                                        e.d_partials);
     } else {
       // COUNT(*) without predicate: the row count is known
-      dev::InitAggStatesCounts(st, 1, cstar, 1, e.stream);
-      unsigned long long c = (unsigned long long)src.n;
-      HIPCHK(hipMemcpyAsync(cstar, &c, 8, hipMemcpyHostToDevice, e.stream));
-      HIPCHK(hipStreamSynchronize(e.stream));
+      known_count();
     }
   }
   out = EmitOneRow(

@@ -8,6 +8,7 @@
 #include "group_direct_plan.h"
 #include "group_pred_plan.h"
 #include "scan_codes.h"
+#include "scan_planes.h"
 #include "str_match.h"
 #include "vm.h"
 
@@ -98,6 +99,17 @@ int FilterAggCodes(const void *codes, int fields, int64_t base, uint32_t clo, ui
 // ceil(end / fields) - 1 (both buffers 256-B aligned at row 0)
 void ScanEncode(const void *values, int phys, void *codes, int fields, int64_t base, int64_t begin, int64_t end,
                 hipStream_t s);
+// The same over a column's bit-plane image (scan_planes.h) of b-bit codes of
+// value - base: reads plane positions 0 .. planes_read - 1 (PlanScanPlanes;
+// all b with `sum`) and tests code >= clo (`ge`) and code <= chi (`le`).
+// Always writes per-workgroup partials and returns their count (> 0).
+int FilterAggPlanes(const void *planes, int b, int planes_read, bool ge, bool le, uint32_t clo, uint32_t chi,
+                    int64_t base, bool sum, bool need_minmax, int64_t nrows, AggPartial *partials, hipStream_t s);
+// Rebuilds from the values of a P_I32 / P_I64 column every word of every plane
+// that holds a row of [begin, end) (both buffers 256-B aligned at row 0, the
+// image's with whole segments for `end` rows)
+void ScanEncodePlanes(const void *values, int phys, void *planes, int b, int64_t base, int64_t begin, int64_t end,
+                      hipStream_t s);
 
 // --- fused GROUP BY on a small-range integer key (config C3) -------------
 // key in [kmin, kmin + nk) (the NULL group in slot nk - 1 when the key has

@@ -42,16 +42,21 @@ struct DevColumn {
   i128 imin = 0, imax = 0;
   int64_t null_count = 0;
   // code image (scan_codes.h) of a narrow-range P_I32 / P_I64 column without
-  // NULLs: value[i] - code_base for rows [0, code_rows), code_fields to a 32-bit
-  // word, in its own 256-B-aligned buffer of ceil(code_cap / code_fields) words.
-  // Built at ingest once the zone map is folded, extended by appends that fit
-  // the base and the field width, rebuilt when the base moves or the field
-  // width changes, freed when the range outgrows two bytes.  The
-  // fused filter-aggregate streams it in place of the values when code_rows
-  // covers the table; `data` stays the column's truth for every other reader.
+  // NULLs: value[i] - code_base for rows [0, code_rows), in its own 256-B-aligned
+  // buffer with room for code_cap rows, in one of two layouts, never both:
+  // fields, code_fields codes to a 32-bit word, ceil(code_cap / code_fields)
+  // words; or, for codes of at most 8 bits in a table of
+  // mbx_scan_codes_planes_min_rows rows or more, code_planes bit planes
+  // (scan_planes.h) in whole 2^20-row segments.  Built at ingest once the zone
+  // map is folded, extended by appends that fit the base and the field width
+  // (the bits per code), rebuilt when the base moves, the width changes or the
+  // layout does, freed when the range outgrows two bytes.  The fused
+  // filter-aggregate streams it in place of the values when code_rows covers
+  // the table; `data` stays the column's truth for every other reader.
   void *codes = nullptr;
   std::shared_ptr<void> codes_owner;
-  int code_fields = 0;  // codes per word (ScanCodeFields), 0: no image
+  int code_fields = 0;  // codes per word (ScanCodeFields), 0: no field image
+  int code_planes = 0;  // bits per code (ScanPlaneBits), 0: no plane image
   int64_t code_base = 0, code_rows = 0, code_cap = 0;
 };
 
@@ -180,6 +185,10 @@ struct Options {
   // bytes for a range that fits 8 bits (packing 1..6-bit fields saves at most
   // 0.2 B a row: 3.4 MB, under 0.5 us of streaming, at 2^24 rows)
   int64_t scan_codes_bits_min_rows = (int64_t)1 << 24;
+  // "mbx_scan_codes_planes_min_rows": tables of at least this many rows keep
+  // codes of at most 8 bits as bit planes (scan_planes.h), so that a scan
+  // reads only the planes its predicate needs
+  int64_t scan_codes_planes_min_rows = (int64_t)1 << 24;
   // "mbx_force_peer" (tests): shards on the same device still exchange row
   // results by peer DMA (hipMemcpyPeerAsync), as distinct devices do
   bool force_peer = false;

@@ -126,6 +126,7 @@ Engine &Eng(Connection &c) {
   e.scan_codes = c.opts.scan_codes;
   e.scan_codes_min_rows = c.opts.scan_codes_min_rows;
   e.scan_codes_bits_min_rows = c.opts.scan_codes_bits_min_rows;
+  e.scan_codes_planes_min_rows = c.opts.scan_codes_planes_min_rows;
   SettlePending(e);  // a statement never sees a column before its appended stats
   return e;
 }

@@ -107,36 +107,56 @@ static void Grow(Engine &e, DevColumn &c, int64_t nrows_old, int64_t need) {
 // appended row is rebuilt whole from the values, never read back.  A column is
 // never left partly coded beyond this call: code_rows is nrows or the image
 // is gone.
+// A table of mbx_scan_codes_planes_min_rows rows or more keeps codes of at
+// most 8 bits as bit planes (scan_planes.h) instead of fields: the same rules
+// with the bits per code in place of the field count (the table crossing that
+// floor, or the bits per code changing, rebuilds the image once, as the other
+// kind where the codes outgrow 8 bits), and a regrown buffer takes over the
+// used whole segments.
 void UpdateScanCodes(Engine &e, DevColumn &c, int64_t nrows) {
-  int f = 0;
+  int f = 0, pb = 0;
   if (e.scan_codes && nrows > 0 && nrows >= e.scan_codes_min_rows && c.stats_valid && !c.validity &&
-      c.null_count == 0 && c.data)
+      c.null_count == 0 && c.data) {
     f = ScanCodeFields(c.phys, c.imin, c.imax, nrows >= e.scan_codes_bits_min_rows);
-  if (!f) {
+    if (f && nrows >= e.scan_codes_planes_min_rows) pb = ScanPlaneBits(c.phys, c.imin, c.imax);
+    if (pb) f = 0;
+  }
+  if (!f && !pb) {
     c.codes = nullptr;
     c.codes_owner.reset();
-    c.code_fields = 0;
+    c.code_fields = c.code_planes = 0;
     c.code_base = c.code_rows = c.code_cap = 0;
     return;
   }
-  const bool extend = c.codes && c.code_fields == f && c.code_base == (int64_t)c.imin && c.code_rows <= nrows;
+  const bool extend = c.codes && c.code_fields == f && c.code_planes == pb && c.code_base == (int64_t)c.imin &&
+                      c.code_rows <= nrows;
   const int64_t begin = extend ? c.code_rows : 0;
   if (begin == nrows) return;
   if (!extend || c.code_cap < nrows) {
     const int64_t cap = std::max<int64_t>(nrows, c.capacity);
+    const int64_t bytes = pb ? ScanPlaneBufferBytes(pb, cap) : (ScanCodeWords(f, cap) * 4 + 255) & ~(int64_t)255;
     void *nc = nullptr;
-    HIPCHK(hipMalloc(&nc, (size_t)((ScanCodeWords(f, cap) * 4 + 255) & ~(int64_t)255)));
+    HIPCHK(hipMalloc(&nc, (size_t)bytes));
     if (begin > 0) {
-      HIPCHK(hipMemcpyAsync(nc, c.codes, (size_t)ScanCodeWords(f, begin) * 4, hipMemcpyDeviceToDevice, e.stream));
+      const int64_t used = pb ? ScanPlaneBufferBytes(pb, begin) : ScanCodeWords(f, begin) * 4;
+      HIPCHK(hipMemcpyAsync(nc, c.codes, (size_t)used, hipMemcpyDeviceToDevice, e.stream));
       HIPCHK(hipStreamSynchronize(e.stream));  // before the old image goes
     }
     c.codes_owner = DevOwned(e, nc);
     c.codes = nc;
     c.code_cap = cap;
     c.code_fields = f;
+    c.code_planes = pb;
     c.code_base = (int64_t)c.imin;
   }
-  {
+  if (pb) {
+    const int64_t first = begin / 32 * 32;  // the first row of the first rebuilt word of every plane
+    ProfScope ps(e, "scan_encode",
+                 (double)(nrows - first) * PhysSize(c.phys) +
+                     (double)(ScanPlaneScanBytes(pb, nrows) - ScanPlaneScanBytes(pb, first)),
+                 nrows - first);
+    dev::ScanEncodePlanes(c.data, c.phys, c.codes, pb, c.code_base, begin, nrows, e.stream);
+  } else {
     const int64_t first = begin / f * f;  // the first row of the first rebuilt word
     ProfScope ps(e, "scan_encode",
                  (double)(nrows - first) * PhysSize(c.phys) + (double)(ScanCodeBytes(f, nrows) - ScanCodeBytes(f, first)),

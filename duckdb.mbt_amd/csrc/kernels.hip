@@ -776,6 +776,191 @@ __global__ __launch_bounds__(256) void scan_encode_kernel(const T *__restrict__ 
     words[wi] = o;
   }
 }
+
+// The same ring over a column's bit-plane image (scan_planes.h): a wave's work
+// item is piece q, 8192 rows, and it issues one 16-B-per-lane LDS-DMA load per
+// plane read, NP of them, into its own slot: the 1 KiB of every plane position
+// 0 .. NP - 1 that holds those rows.  A lane then has four words, 128 rows, of
+// every plane.  SIDES (bit 0: code >= clo, bit 1: code <= chi) are the
+// bit-serial compares over the NP planes, klo / khi the bounds' same NP bits.
+// MODE 2 counts; MODE 0 (NP is then all b planes) also sums the passing codes
+// by popcounts, and MM takes their min / max by narrowing a candidate mask.
+// Per piece a lane adds at most 128 to its count and 128 x 255 to its sum in
+// 32-bit piece totals, folded into 64-bit lane totals; the value sum is codes
+// + count x base in int128, once per lane, so the partial records are exactly
+// those of the 8-byte kernel.  The rows past the last whole piece go to wave 0
+// of block 0, by plain loads, the last word masked to n.
+// A wave keeps DEPTH pieces of NP KiB in flight: at least the 6 KiB of the
+// other rings, in a block of at most 64 KiB (DESIGN.md §3 has the depths tried).
+// MBX_SCAN_PLANES_RING_KIB is a build-time knob kept only so that those depth
+// trials can be repeated (make OPT="-O3 -DMBX_SCAN_PLANES_RING_KIB=12"); the
+// shipped library is built without it.
+#ifndef MBX_SCAN_PLANES_RING_KIB
+#define MBX_SCAN_PLANES_RING_KIB 6
+#endif
+constexpr int ScanPlanesDepth(int np) {
+  int d = (MBX_SCAN_PLANES_RING_KIB + np - 1) / np;
+  if (d > 16 / np) d = 16 / np;
+  return d < 2 ? 2 : d;
+}
+template <int NP, int SIDES, int MODE, bool MM>
+__global__ __launch_bounds__(256) void filter_agg_planes_kernel(const uint32_t *__restrict__ planes, int64_t n, int b,
+                                                                uint32_t klo, uint32_t khi, int64_t base,
+                                                                AggPartial *partials) {
+  constexpr int DEPTH = ScanPlanesDepth(NP);
+  __shared__ __attribute__((aligned(16))) v4i32 ring[4 * DEPTH * NP * 64];
+  static_assert(sizeof(v4i32) * 4 * DEPTH * NP * 64 <= 65536 && NP * (DEPTH - 1) <= 63, "the ring fits a block and vmcnt");
+  static_assert(sizeof(v4i32) * 4 * DEPTH * NP * 64 >= 4 * sizeof(Acc), "the block reduction reuses the ring");
+  static_assert(MODE == 0 || (MODE == 2 && !MM && SIDES != 0), "MIN / MAX come with the sum; a count tests a side");
+  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int64_t npieces = n / kScanPlanePieceRows;
+  const int64_t nw = (int64_t)gridDim.x * 4;
+  int64_t pc = (int64_t)blockIdx.x * 4 + w;
+  v4i32 *slot0 = ring + w * DEPTH * NP * 64;
+  const char *P = (const char *)planes + lane * 16;
+  uint64_t cnt = 0, sum = 0;
+  int32_t mn = INT32_MAX, mx = -1;  // codes are below 2^8
+  // the 32 rows `rows` of one word index: p[k] is the word of plane position k
+  auto word = [&](const uint32_t *p, uint32_t rows, uint32_t &pcnt, uint32_t &psum) {
+    uint32_t m = rows;
+    if (SIDES & 1) m &= ScanPlanesGe(p, NP, klo);
+    if (SIDES & 2) m &= ScanPlanesLe(p, NP, khi);
+    pcnt += __builtin_popcount(m);
+    if (MODE == 0) psum += ScanPlanesSum(p, NP, m);
+    if (MM) {
+      mn = min(mn, m ? (int32_t)ScanPlanesMin(p, NP, m) : INT32_MAX);
+      mx = max(mx, m ? (int32_t)ScanPlanesMax(p, NP, m) : -1);
+    }
+  };
+  auto issue = [&](int64_t q, int d) {
+#pragma unroll
+    for (int k = 0; k < NP; k++)
+      __builtin_amdgcn_global_load_lds((const void *)(P + ScanPlanePieceByte(b, k, q)), (void *)(slot0 + (d * NP + k) * 64),
+                                       16, 0, 2);
+  };
+#pragma unroll
+  for (int d = 0; d < DEPTH; d++) {
+    int64_t q = pc + d * nw;
+    q = q < npieces ? q : 0;  // keep the per-slot load count uniform (dummy piece 0)
+    if (npieces > 0) issue(q, d);
+  }
+  int kk = 0;
+  for (; pc < npieces; pc += nw) {
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NP * (DEPTH - 1)) : "memory");
+    v4i32 x[NP];
+#pragma unroll
+    for (int k = 0; k < NP; k++) x[k] = slot0[(kk * NP + k) * 64 + lane];
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    int64_t q = pc + DEPTH * nw;
+    q = q < npieces ? q : pc;  // past the end: re-read the piece just consumed
+    issue(q, kk);
+    uint32_t pcnt = 0, psum = 0;
+#pragma unroll
+    for (int e = 0; e < 4; e++) {
+      uint32_t p[NP];
+#pragma unroll
+      for (int k = 0; k < NP; k++) p[k] = (uint32_t)x[k][e];
+      word(p, ~0u, pcnt, psum);
+    }
+    cnt += pcnt;
+    sum += psum;
+    kk = kk + 1 == DEPTH ? 0 : kk + 1;
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  if (blockIdx.x == 0 && w == 0) {
+    const int64_t r0 = npieces * kScanPlanePieceRows, tw = ScanPlaneWords(n - r0);  // at most 256 words a plane
+    uint32_t pcnt = 0, psum = 0;
+    for (int64_t i = lane; i < tw; i += 64) {
+      uint32_t p[NP];
+#pragma unroll
+      for (int k = 0; k < NP; k++) p[k] = planes[ScanPlaneWord(b, k, r0 + i * 32)];
+      word(p, i == tw - 1 ? ScanPlaneLastWordMask(n) : ~0u, pcnt, psum);
+    }
+    cnt += pcnt;
+    sum += psum;
+  }
+  Acc A;
+  A.cnt = cnt;
+  {
+    const __int128 s = (__int128)(unsigned __int128)sum + (__int128)(unsigned __int128)cnt * (__int128)base;
+    A.slo = (uint64_t)s;
+    A.shi = (int64_t)(s >> 64);
+  }
+  A.mn = MM && mx >= 0 ? (int64_t)((uint64_t)base + (uint64_t)mn) : INT64_MAX;
+  A.mx = MM && mx >= 0 ? (int64_t)((uint64_t)base + (uint64_t)mx) : INT64_MIN;
+  acc_wave_reduce(A);
+  __syncthreads();
+  Acc *part = (Acc *)ring;
+  if (lane == 0) part[w] = A;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    Acc T0 = part[0];
+    for (int i = 1; i < 4; i++) acc_merge(T0, part[i]);
+    partials[blockIdx.x] = AggPartial{T0.cnt, T0.slo, T0.shi, T0.mn, T0.mx};
+  }
+}
+
+// Builds the words of every plane of the bit-plane image that hold rows
+// [begin, end): each plane's words from begin / 32 on are made whole from the
+// values (the bits of rows >= end stay zero) and never read back.  A block
+// takes one piece of 8192 rows at a time: the values come in as coalesced
+// 16-byte loads (singly where a load would cross `end`), their codes go to LDS
+// as bytes, and thread t gathers the 32 codes of word t into one word per
+// plane, four rows at a time: the multiply moves bit 0 of the four bytes of
+// ((d >> j) & 0x01010101) to bits 24 .. 27.  So a block owns whole words, the
+// 256 threads store 1 KiB of each plane side by side, and a piece lands at
+// ScanPlanePieceByte whichever segment it is in.
+template <typename T>
+__global__ __launch_bounds__(256) void scan_encode_planes_kernel(const T *__restrict__ v, uint32_t *__restrict__ planes,
+                                                                 int b, int64_t begin, int64_t end, uint64_t base) {
+  constexpr int R = 16 / (int)sizeof(T);                   // rows per 16-byte load
+  constexpr int UNITS = (int)kScanPlanePieceRows / R;      // 16-byte loads per piece
+  __shared__ __attribute__((aligned(16))) uint8_t lds[kScanPlanePieceRows];
+  const int64_t w0 = begin / 32;
+  const int64_t q0 = begin / kScanPlanePieceRows, q1 = (end + kScanPlanePieceRows - 1) / kScanPlanePieceRows;
+  for (int64_t q = q0 + blockIdx.x; q < q1; q += gridDim.x) {
+    const int64_t r0 = q * kScanPlanePieceRows;
+    for (int u = threadIdx.x; u < UNITS; u += 256) {
+      const int64_t r = r0 + (int64_t)u * R;
+      uint32_t c[R];
+      if (r + R <= end) {
+        const v4i32 x = __builtin_nontemporal_load((const v4i32 *)(v + r));
+        if (sizeof(T) == 8) {
+          c[0] = (uint32_t)x.x - (uint32_t)base;  // the low byte of value - base needs the low words only
+          c[1 % R] = (uint32_t)x.z - (uint32_t)base;
+        } else {
+#pragma unroll
+          for (int e = 0; e < R; e++) c[e] = (uint32_t)x[e] - (uint32_t)base;
+        }
+      } else {
+#pragma unroll
+        for (int e = 0; e < R; e++) c[e] = r + e < end ? (uint32_t)(uint64_t)(int64_t)v[r + e] - (uint32_t)base : 0u;
+      }
+      if (sizeof(T) == 8) {
+        ((uint16_t *)lds)[u] = (uint16_t)((c[0] & 0xFFu) | ((c[1 % R] & 0xFFu) << 8));
+      } else {
+        ((uint32_t *)lds)[u] = (c[0] & 0xFFu) | ((c[1 % R] & 0xFFu) << 8) | ((c[2 % R] & 0xFFu) << 16) | (c[3 % R] << 24);
+      }
+    }
+    __syncthreads();
+    const int64_t row = r0 + (int64_t)threadIdx.x * 32, wi = row / 32;
+    if (row < end && wi >= w0) {
+      uint32_t d[8];
+      const uint4 lo = ((const uint4 *)lds)[threadIdx.x * 2], hi = ((const uint4 *)lds)[threadIdx.x * 2 + 1];
+      d[0] = lo.x; d[1] = lo.y; d[2] = lo.z; d[3] = lo.w;
+      d[4] = hi.x; d[5] = hi.y; d[6] = hi.z; d[7] = hi.w;
+      for (int k = 0; k < b; k++) {
+        const int j = b - 1 - k;
+        uint32_t o = 0;
+#pragma unroll
+        for (int i = 0; i < 8; i++) o |= ((((d[i] >> j) & 0x01010101u) * 0x01020408u) >> 24) << (4 * i);
+        planes[ScanPlaneWord(b, k, row)] = o;
+      }
+    }
+    __syncthreads();
+  }
+}
+
 // Multi-column version of the LDS-DMA filter-aggregate.  A wave step covers
 // 256 consecutive rows; each column's slice (1 KiB for int32, 2 KiB for
 // int64) lands in the wave's ring slot through global_load_lds; each lane
@@ -1223,6 +1408,66 @@ void ScanEncode(const void *values, int phys, void *codes, int fields, int64_t b
 #undef X
     default: throw std::runtime_error("ScanEncode: no kernel for " + std::to_string(fields) + " fields per word");
   }
+  CHECK_LAUNCH();
+}
+
+template <int NP>
+static void LaunchFilterAggPlanes(const void *planes, int b, int sides, uint32_t klo, uint32_t khi, int64_t base,
+                                  bool sum, bool mm, int64_t nrows, AggPartial *partials, int grid, hipStream_t s) {
+#define FAP(SIDES, MODE, MM)                                                                              \
+  hipLaunchKernelGGL((filter_agg_planes_kernel<NP, SIDES, MODE, MM>), dim3(grid), dim3(256), 0, s,        \
+                     (const uint32_t *)planes, nrows, b, klo, khi, base, partials)
+#define FAP_S(MODE, MM)                   \
+  switch (sides) {                        \
+    case 1: FAP(1, MODE, MM); break;      \
+    case 2: FAP(2, MODE, MM); break;      \
+    default: FAP(3, MODE, MM); break;     \
+  }
+  // a COUNT(*) that tests no side reads no plane and never gets here (FilterAggPlanes)
+  if (sides == 0) {
+    if (mm) FAP(0, 0, true);
+    else FAP(0, 0, false);
+  } else if (!sum) { FAP_S(2, false) }
+  else if (mm) { FAP_S(0, true) }
+  else { FAP_S(0, false) }
+#undef FAP_S
+#undef FAP
+}
+
+int FilterAggPlanes(const void *planes, int b, int planes_read, bool ge, bool le, uint32_t clo, uint32_t chi,
+                    int64_t base, bool sum, bool need_minmax, int64_t nrows, AggPartial *partials, hipStream_t s) {
+  if (planes_read < 1 || planes_read > b || b > kScanPlaneMaxBits || (sum && planes_read != b) || (!sum && !ge && !le))
+    throw std::runtime_error("FilterAggPlanes: no kernel for " + std::to_string(planes_read) + " of " +
+                             std::to_string(b) + " planes");
+  int grid = NumCUs();
+  if (grid > kMaxAggPartials) grid = kMaxAggPartials;
+  const int64_t pieces = nrows / kScanPlanePieceRows + 1;
+  if ((int64_t)grid * 4 > pieces) grid = (int)((pieces + 3) / 4);
+  const int sides = (ge ? 1 : 0) | (le ? 2 : 0), shift = b - planes_read;
+  switch (planes_read) {
+#define X(NP)                                                                                                  \
+  case NP:                                                                                                     \
+    LaunchFilterAggPlanes<NP>(planes, b, sides, clo >> shift, chi >> shift, base, sum, sum && need_minmax,     \
+                              nrows, partials, grid, s);                                                       \
+    break;
+    X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8)
+#undef X
+  }
+  CHECK_LAUNCH();
+  return grid;
+}
+
+void ScanEncodePlanes(const void *values, int phys, void *planes, int b, int64_t base, int64_t begin, int64_t end,
+                      hipStream_t s) {
+  if (end <= begin) return;
+  const int64_t pieces = (end + kScanPlanePieceRows - 1) / kScanPlanePieceRows - begin / kScanPlanePieceRows;
+  const int grid = (int)std::min<int64_t>(pieces, (int64_t)NumCUs() * 8);
+  if (phys == P_I64)
+    hipLaunchKernelGGL((scan_encode_planes_kernel<int64_t>), dim3(grid), dim3(256), 0, s, (const int64_t *)values,
+                       (uint32_t *)planes, b, begin, end, (uint64_t)base);
+  else
+    hipLaunchKernelGGL((scan_encode_planes_kernel<int32_t>), dim3(grid), dim3(256), 0, s, (const int32_t *)values,
+                       (uint32_t *)planes, b, begin, end, (uint64_t)base);
   CHECK_LAUNCH();
 }
 
