@@ -1281,6 +1281,106 @@ int64_t ConstInt(const Expr &e, const std::vector<Value> &params, const char *wh
 // ---------------------------------------------------------------------------
 static BoundSelectPtr BindSelectOne(const Select &sel, Catalog &cat, const std::vector<Value> &params);
 
+// The columns a source offers to name resolution, leaf by leaf: a join's are
+// its left input's and then its right input's, each under its own alias, so the
+// position in the scope is the column of the source relation.
+static void SourceScope(const BoundSource &src, std::vector<ScopeCol> &out) {
+  if (src.kind == BoundSource::JOIN) {
+    SourceScope(*src.left, out);
+    SourceScope(*src.right, out);
+    return;
+  }
+  for (size_t i = 0; i < src.col_names.size(); i++) out.push_back({src.col_names[i], src.alias, src.col_types[i]});
+}
+
+static void JoinLeaves(const BoundSource &src, std::vector<const BoundSource *> &out) {
+  if (src.kind == BoundSource::JOIN) {
+    JoinLeaves(*src.left, out);
+    JoinLeaves(*src.right, out);
+  } else {
+    out.push_back(&src);
+  }
+}
+
+static void FlattenAnd(const ExprPtr &e, std::vector<ExprPtr> &out) {
+  if (e->kind == Expr::BINARY && e->op == "AND") {
+    FlattenAnd(e->args[0], out);
+    FlattenAnd(e->args[1], out);
+  } else {
+    out.push_back(e);
+  }
+}
+
+// bit 0: the tree reads a column below `nleft`, bit 1: one at or above it
+static int JoinSides(const BExpr &e, int nleft) {
+  int m = e.kind == BExpr::COL ? (e.col < nleft ? 1 : 2) : 0;
+  for (auto &c : e.ch) m |= JoinSides(*c, nleft);
+  return m;
+}
+
+// renumbers the column references of a right-side key from the joined columns
+// to the right input's own, in place (a parameter's constant node must stay the
+// node the plan holds); a node shared by two parents moves once
+static void ShiftCols(BExpr &e, int by, std::set<const BExpr *> &seen) {
+  if (!seen.insert(&e).second) return;
+  if (e.kind == BExpr::COL) e.col -= by;
+  for (auto &c : e.ch) ShiftCols(*c, by, seen);
+}
+
+// ON of an inner join: the first conjunct l = r with l over one input and r
+// over the other, of a type stored as an integer of at most 8 bytes, is the
+// key; every other conjunct is the residual.
+static void BindJoinCondition(const TableRef &tr, BoundSource &src, const std::vector<Value> &params) {
+  std::vector<const BoundSource *> leaves;
+  JoinLeaves(src, leaves);
+  std::set<std::string> aliases;
+  for (auto *l : leaves) {
+    if (l->kind == BoundSource::TABLE && l->table && l->table->sharded())
+      ThrowError("Not implemented", "a join over table \"" + l->table->name +
+                                        "\", which is sharded by gpu_devices, is not supported by the MI355X backend");
+    if (!aliases.insert(Lower(l->alias)).second) ThrowError("Binder", "Duplicate alias \"" + l->alias + "\" in query!");
+  }
+  src.col_types = src.left->col_types;
+  src.col_names = src.left->col_names;
+  src.col_types.insert(src.col_types.end(), src.right->col_types.begin(), src.right->col_types.end());
+  src.col_names.insert(src.col_names.end(), src.right->col_names.begin(), src.right->col_names.end());
+  const int nleft = (int)src.left->col_types.size();
+  BindCtx ctx;
+  ctx.params = &params;
+  SourceScope(src, ctx.scope);
+  std::vector<ExprPtr> conj;
+  FlattenAnd(tr.on, conj);
+  LogicalType refused;  // the type of a two-sided equality that cannot be a key
+  for (auto &cj : conj) {
+    if (ContainsAgg(*cj)) ThrowError("Binder", "JOIN condition cannot contain aggregates!");
+    BExprPtr b = CastTo(BindExpr(*cj, ctx), LogicalType(T_BOOLEAN));
+    if (!src.left_key && b->kind == BExpr::FUNC && b->op == B_EQ && b->ch.size() == 2) {
+      const int s0 = JoinSides(*b->ch[0], nleft), s1 = JoinSides(*b->ch[1], nleft);
+      if ((s0 == 1 && s1 == 2) || (s0 == 2 && s1 == 1)) {
+        const LogicalType &t = b->ch[0]->type;
+        if (PhysOf(t) <= P_U64) {
+          src.left_key = b->ch[s0 == 1 ? 0 : 1];
+          src.right_key = b->ch[s0 == 1 ? 1 : 0];
+          src.key_type = t;
+          std::set<const BExpr *> seen;
+          ShiftCols(*src.right_key, nleft, seen);
+          continue;
+        }
+        if (refused.id == T_INVALID) refused = t;
+      }
+    }
+    src.residual = src.residual ? MkFunc(B_AND, LogicalType(T_BOOLEAN), {src.residual, b}) : b;
+  }
+  if (!src.left_key) {
+    if (refused.id != T_INVALID)
+      ThrowError("Not implemented", "a join key of type " + refused.ToString() +
+                                        " is not supported by the MI355X backend (keys stored as integers of at most 8 bytes only)");
+    ThrowError("Not implemented",
+               "a JOIN whose ON clause has no equality between an expression over the left input and one over the right "
+               "input is not supported by the MI355X backend");
+  }
+}
+
 static void BindSource(const TableRef &tr, BoundSource &src, Catalog &cat, const std::vector<Value> &params) {
   switch (tr.kind) {
     case TableRef::NONE:
@@ -1356,6 +1456,15 @@ static void BindSource(const TableRef &tr, BoundSource &src, Catalog &cat, const
       src.alias = tr.alias.empty() ? "unnamed_subquery" : tr.alias;
       break;
     }
+    case TableRef::JOIN: {
+      src.kind = BoundSource::JOIN;
+      src.left = std::make_shared<BoundSource>();
+      src.right = std::make_shared<BoundSource>();
+      BindSource(*tr.left, *src.left, cat, params);
+      BindSource(*tr.right, *src.right, cat, params);
+      BindJoinCondition(tr, src, params);
+      break;
+    }
   }
   if (!tr.col_aliases.empty()) {
     if (tr.col_aliases.size() > src.col_names.size())
@@ -1370,21 +1479,26 @@ static BoundSelectPtr BindSelectOne(const Select &sel, Catalog &cat, const std::
   BindSource(sel.from, bs->src, cat, params);
   BindCtx base;
   base.params = &params;
-  for (size_t i = 0; i < bs->src.col_names.size(); i++)
-    base.scope.push_back({bs->src.col_names[i], bs->src.alias, bs->src.col_types[i]});
+  SourceScope(bs->src, base.scope);
   base.select_list = &sel.list;
 
-  // expand *
+  // expand * and alias.*: over a join every reference carries its input's
+  // alias (both inputs may own a column of one name)
   std::vector<ExprPtr> list;
   for (auto &e : sel.list) {
     if (e->kind == Expr::STAR) {
       if (bs->src.kind == BoundSource::ONE_ROW) ThrowError("Binder", "SELECT * expression without FROM clause!");
-      for (size_t i = 0; i < bs->src.col_names.size(); i++) {
+      size_t before = list.size();
+      for (const ScopeCol &sc : base.scope) {
+        if (!e->qualifier.empty() && Lower(sc.qualifier) != Lower(e->qualifier)) continue;
         auto c = std::make_shared<Expr>();
         c->kind = Expr::COLREF;
-        c->name = bs->src.col_names[i];
+        c->name = sc.name;
+        if (bs->src.kind == BoundSource::JOIN) c->qualifier = sc.qualifier;
         list.push_back(c);
       }
+      if (!e->qualifier.empty() && list.size() == before)
+        ThrowError("Binder", "Referenced table \"" + e->qualifier + "\" not found!");
     } else {
       list.push_back(e);
     }
@@ -1491,8 +1605,7 @@ BoundSelectPtr BindSelect(const Select &sel, Catalog &cat, const std::vector<Val
       // hidden sort key: bind over the source (or the aggregate relation)
       BindCtx ctx;
       ctx.params = &params;
-      for (size_t i = 0; i < first->src.col_names.size(); i++)
-        ctx.scope.push_back({first->src.col_names[i], first->src.alias, first->src.col_types[i]});
+      SourceScope(first->src, ctx.scope);
       if (first->is_agg) {
         ctx.agg_mode = true;
         ctx.groups = &first->groups;
@@ -1520,6 +1633,29 @@ bool IsHostConstantSelect(const BoundSelect &s) {
   return true;
 }
 
+static std::string ExplainSource(const BoundSource &src, int ind, const char *lead) {
+  std::string pad(ind, ' ');
+  switch (src.kind) {
+    case BoundSource::ONE_ROW: return pad + lead + "<one row>\n";
+    case BoundSource::RANGE:
+      return pad + lead + "RANGE(" + std::to_string(src.range_start) + ", " + std::to_string(src.range_stop) + ", " +
+             std::to_string(src.range_step) + (src.range_inclusive ? ", inclusive" : "") + ")\n";
+    case BoundSource::TABLE: return pad + lead + "TABLE " + src.table->name + "\n";
+    case BoundSource::VALUES: return pad + lead + "VALUES[" + std::to_string(src.rows.size()) + " rows]\n";
+    case BoundSource::SUBQUERY: return pad + lead + "(\n" + ExplainSelect(*src.sub, ind + 4) + pad + ")\n";
+    case BoundSource::JOIN: {
+      // keys print over their own input's columns, the residual over the joined ones
+      std::string out = pad + lead + "HASH JOIN key " + src.key_type.ToString() + ": left " + ExprToString(*src.left_key) +
+                        " = right " + ExprToString(*src.right_key) + "\n";
+      if (src.residual) out += pad + "  RESIDUAL " + ExprToString(*src.residual) + "\n";
+      out += ExplainSource(*src.left, ind + 2, "LEFT ");
+      out += ExplainSource(*src.right, ind + 2, "RIGHT ");
+      return out;
+    }
+  }
+  return "";
+}
+
 std::string ExplainSelect(const BoundSelect &s, int ind) {
   std::string pad(ind, ' ');
   std::string out;
@@ -1527,16 +1663,8 @@ std::string ExplainSelect(const BoundSelect &s, int ind) {
   for (size_t i = 0; i < s.outputs.size(); i++)
     out += (i ? ", " : " ") + ExprToString(*s.outputs[i]) + " AS " + s.names[i] + " :: " + s.outputs[i]->type.ToString();
   out += "\n";
-  switch (s.src.kind) {
-    case BoundSource::ONE_ROW: out += pad + "  FROM <one row>\n"; break;
-    case BoundSource::RANGE:
-      out += pad + "  FROM RANGE(" + std::to_string(s.src.range_start) + ", " + std::to_string(s.src.range_stop) + ", " +
-             std::to_string(s.src.range_step) + (s.src.range_inclusive ? ", inclusive" : "") + ")\n";
-      break;
-    case BoundSource::TABLE: out += pad + "  FROM TABLE " + s.src.table->name + "\n"; break;
-    case BoundSource::VALUES: out += pad + "  FROM VALUES[" + std::to_string(s.src.rows.size()) + " rows]\n"; break;
-    case BoundSource::SUBQUERY: out += pad + "  FROM (\n" + ExplainSelect(*s.src.sub, ind + 4) + pad + "  )\n"; break;
-  }
+  if (s.src.kind == BoundSource::SUBQUERY) out += pad + "  FROM (\n" + ExplainSelect(*s.src.sub, ind + 4) + pad + "  )\n";
+  else out += ExplainSource(s.src, ind + 2, "FROM ");
   if (s.where) out += pad + "  WHERE " + ExprToString(*s.where) + "\n";
   if (s.is_agg) {
     out += pad + "  AGGREGATE groups=[";
@@ -1569,6 +1697,17 @@ static void CollectExprNodes(const BExpr *e, std::set<const BExpr *> &out) {
   for (auto &c : e->ch) CollectExprNodes(c.get(), out);
 }
 
+static void CollectPlanNodes(const BoundSelect &s, std::set<const BExpr *> &out);
+static void CollectSourceNodes(const BoundSource &src, std::set<const BExpr *> &out) {
+  if (src.sub) CollectPlanNodes(*src.sub, out);
+  if (src.kind != BoundSource::JOIN) return;
+  CollectExprNodes(src.left_key.get(), out);
+  CollectExprNodes(src.right_key.get(), out);
+  CollectExprNodes(src.residual.get(), out);
+  CollectSourceNodes(*src.left, out);
+  CollectSourceNodes(*src.right, out);
+}
+
 static void CollectPlanNodes(const BoundSelect &s, std::set<const BExpr *> &out) {
   CollectExprNodes(s.where.get(), out);
   CollectExprNodes(s.having.get(), out);
@@ -1576,7 +1715,7 @@ static void CollectPlanNodes(const BoundSelect &s, std::set<const BExpr *> &out)
   for (auto &a : s.aggs) CollectExprNodes(a.arg.get(), out);
   for (auto &o : s.outputs) CollectExprNodes(o.get(), out);
   for (auto &o : s.order) CollectExprNodes(o.expr.get(), out);
-  if (s.src.sub) CollectPlanNodes(*s.src.sub, out);
+  CollectSourceNodes(s.src, out);
   for (auto &u : s.union_all) CollectPlanNodes(*u, out);
 }
 

@@ -13,6 +13,7 @@
 #include "vm.h"
 
 namespace mbx {
+struct JoinEntry;  // join_plan.h
 namespace dev {
 
 // validity[w] = ~nullbits[w] over the words covering n rows (tail bits cleared)
@@ -290,6 +291,19 @@ constexpr int kCalibrateShapes = 8;  // HbmCalibrate's measured shapes (kernels.
 void HbmCalibrate(void *buf_a, void *buf_b, int64_t bytes, int iters, double out[kCalibrateShapes], hipStream_t s);
 // clock stamps of the last stamped launch (libduckdb_mb_amd_clk.so only; 0 otherwise)
 int ReadClockStamps(uint64_t *out, int cap, hipStream_t s);
+
+// --- inner equi-join (join_kernels.hip; table layout and walks: join_plan.h) ---
+// keys[i] = the integer column's row i sign- or zero-extended; rows[i] = i (rows may be null)
+void JoinKeys(const void *col, int phys, int64_t n, int64_t *keys, int64_t *rows, hipStream_t s);
+// sorted_keys: the build keys in sorted order; tab: cap zeroed entries
+void JoinBuild(const int64_t *sorted_keys, int64_t n, JoinEntry *tab, int64_t cap, int32_t *err, hipStream_t s);
+// counts[i] = build rows that match probe row i (0 for a NULL key), starts[i] = their run's start
+void JoinProbeCount(const void *col, int phys, const uint64_t *valid, int64_t n, const JoinEntry *tab, int64_t cap,
+                    int64_t *counts, int32_t *starts, int32_t *err, hipStream_t s);
+// offsets: ScanLengths of counts (n + 1 entries, offsets[n] == total); build_rows: the build row
+// numbers in sorted-key order.  Writes the total pairs, probe-row-major, build rows ascending.
+void JoinExpand(const int64_t *offsets, const int32_t *starts, int64_t n, int64_t total, const int64_t *build_rows,
+                int64_t *out_probe, int64_t *out_build, hipStream_t s);
 
 int NumCUs();
 

@@ -189,6 +189,10 @@ struct Options {
   // codes of at most 8 bits as bit planes (scan_planes.h), so that a scan
   // reads only the planes its predicate needs
   int64_t scan_codes_planes_min_rows = (int64_t)1 << 24;
+  // "mbx_join_max_rows": a join whose matches number more than this fails
+  // with an Out of Range error before its result is allocated (one accidental
+  // near-cross-product must not ask a shared card's pool for hundreds of GB)
+  int64_t join_max_rows = 2147483647;
   // "mbx_force_peer" (tests): shards on the same device still exchange row
   // results by peer DMA (hipMemcpyPeerAsync), as distinct devices do
   bool force_peer = false;

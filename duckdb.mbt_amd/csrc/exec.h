@@ -1,7 +1,7 @@
 // exec.h — what the executor's translation units share (executor.cpp,
-// aggregate.cpp, ingest.cpp, sharded.cpp): the engine state, device buffers
+// aggregate.cpp, join.cpp, ingest.cpp, sharded.cpp): the engine state, device buffers
 // and relations, and the functions that cross between the units.  Internal to
-// those four files: the engine and the C-ABI shim see engine.h only.
+// those five files: the engine and the C-ABI shim see engine.h only.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -311,6 +311,7 @@ DRel GatherRel(Engine &e, const DRel &r, const int64_t *perm, int64_t n);
 DRel ConcatRels(Engine &e, std::vector<DRel> &parts);
 ResultPtr ToHost(Engine &e, const DRel &r, const std::vector<std::string> &names, int64_t offset, int64_t limit,
                  size_t ncols, bool text = false);
+DRel SourceRel(Engine &e, Connection &c, const BoundSource &src);
 DRel RunBranch(Engine &e, Connection &c, const BoundSelect &s);
 size_t VisibleCols(const BoundSelect &s);
 DRel RunSelectDev(Engine &e, Connection &c, const BoundSelect &s, bool top = false);
@@ -319,6 +320,8 @@ ResultPtr HostConstantSelect(const BoundSelect &s);
 void FinishProfile(Connection &c, Engine &e, double total_ms);
 // ---- aggregate.cpp
 DRel Aggregate(Engine &e, const DRel &src, const BoundSelect &s);
+// ---- join.cpp
+DRel JoinRel(Engine &e, Connection &c, const BoundSource &src);
 // ---- ingest.cpp
 void UpdateScanCodes(Engine &e, DevColumn &c, int64_t nrows);
 void AppendCast(Engine &e, Table &t, DRel r, const std::vector<int> &col_map);

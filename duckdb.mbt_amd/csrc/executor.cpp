@@ -178,6 +178,7 @@ void RaiseDeviceError(Engine &e, int32_t err) {
       case E_CAST_RANGE: ThrowError("Conversion", "Value out of range for the destination type in CAST");
       case E_HASH_FULL: ThrowError("Internal", "hash aggregate table overflow");
       case E_KEY_RANGE: ThrowError("Internal", "GROUP BY key outside its column statistics");
+      case E_JOIN_FULL: ThrowError("Internal", "join table full");
       default: ThrowError("Out of Range", "Decimal value out of range");
     }
   }
@@ -1568,7 +1569,7 @@ ResultPtr ToHost(Engine &e, const DRel &r, const std::vector<std::string> &names
 // ---------------------------------------------------------------------------
 // select
 // ---------------------------------------------------------------------------
-static DRel SourceRel(Engine &e, Connection &c, const BoundSource &src) {
+DRel SourceRel(Engine &e, Connection &c, const BoundSource &src) {
   DRel r;
   switch (src.kind) {
     case BoundSource::ONE_ROW:
@@ -1596,6 +1597,9 @@ static DRel SourceRel(Engine &e, Connection &c, const BoundSource &src) {
     case BoundSource::SUBQUERY:
       r = RunSelectDev(e, c, *src.sub);
       // hidden order keys of the subquery are dropped by RunSelectDev
+      break;
+    case BoundSource::JOIN:
+      r = JoinRel(e, c, src);
       break;
   }
   return r;

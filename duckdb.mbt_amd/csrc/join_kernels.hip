@@ -1,0 +1,270 @@
+// join_kernels.hip — the inner equi-join on the device (executor: join.cpp).
+//
+//   join_keys         build keys of any integer width -> int64 (sign- or
+//                     zero-extended) and, beside them, their row numbers
+//   join_build        over the SORTED build keys: the first row of every run of
+//                     equal keys inserts {key, run start, run length} into the
+//                     open-addressing table of join_plan.h (one CAS per key)
+//   join_probe_count  per probe row: hash, walk, write the match count (int64)
+//                     and the run start (int32); no atomics on this side
+//   join_expand       per OUTPUT row j in [0, total): the probe row whose
+//                     [offsets[p], offsets[p + 1]) holds j and the build row at
+//                     that place of its run
+//
+// Every lane owns two consecutive rows, so 8-byte columns move as 16 bytes per
+// lane.  join_expand is laid out by output rows, not by probe rows: a probe
+// row with a million matches is a million output rows spread over as many
+// lanes as any other million, and nothing is written outside [0, total).
+// Every table walk is bounded by the capacity (join_plan.h); a walk that runs
+// out raises E_JOIN_FULL in the device error word.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <algorithm>
+#include <stdexcept>
+#include <string>
+
+#include "device.h"
+#include "join_plan.h"
+#include "phys.h"
+#include "vm.h"
+
+namespace mbx {
+namespace dev {
+
+namespace {
+
+constexpr int kJoinBlock = 256;
+constexpr int kJoinBlocksPerCU = 8;
+constexpr int kExpandTile = 2 * kJoinBlock;  // output rows of a workgroup step
+
+int PairGrid(int64_t n) {
+  const int64_t pairs = (n + 1) / 2;
+  const int64_t want = (pairs + kJoinBlock - 1) / kJoinBlock;
+  return (int)std::max<int64_t>(1, std::min<int64_t>(want, (int64_t)NumCUs() * kJoinBlocksPerCU));
+}
+
+__device__ __forceinline__ bool row_valid(const uint64_t *__restrict__ valid, int64_t i) {
+  return !valid || ((valid[i >> 6] >> (i & 63)) & 1);
+}
+
+// rows i0, i0 + 1 of a column as int64; 8-byte columns with one 16-B load
+template <typename T>
+__device__ __forceinline__ void load_pair(const T *__restrict__ col, int64_t i0, bool both, int64_t &a, int64_t &b) {
+  if constexpr (sizeof(T) == 8) {
+    if (both && (((uintptr_t)col & 15) == 0)) {
+      const longlong2 v = *(const longlong2 *)(col + i0);
+      a = v.x, b = v.y;
+      return;
+    }
+  }
+  a = (int64_t)col[i0];
+  b = both ? (int64_t)col[i0 + 1] : a;
+}
+
+__device__ __forceinline__ void store_pair(int64_t *__restrict__ out, int64_t i0, bool both, int64_t a, int64_t b) {
+  if (both && (((uintptr_t)out & 15) == 0)) {
+    *(longlong2 *)(out + i0) = make_longlong2(a, b);
+  } else {
+    out[i0] = a;
+    if (both) out[i0 + 1] = b;
+  }
+}
+
+template <typename T>
+__global__ __launch_bounds__(kJoinBlock) void join_keys_kernel(const T *__restrict__ col, const int64_t n,
+                                                               int64_t *__restrict__ keys, int64_t *__restrict__ rows) {
+  const int64_t stride = (int64_t)gridDim.x * kJoinBlock;
+  for (int64_t t = (int64_t)blockIdx.x * kJoinBlock + threadIdx.x; 2 * t < n; t += stride) {
+    const int64_t i0 = 2 * t;
+    const bool both = i0 + 1 < n;
+    int64_t a, b;
+    load_pair(col, i0, both, a, b);
+    store_pair(keys, i0, both, a, b);
+    if (rows) store_pair(rows, i0, both, i0, i0 + 1);
+  }
+}
+
+// rows of the run of equal keys that starts at i: gallop, then bisect
+__device__ __forceinline__ int64_t run_length(const int64_t *__restrict__ keys, int64_t n, int64_t i, int64_t k) {
+  int64_t step = 1;
+  while (i + step < n && keys[i + step] == k) step <<= 1;
+  // keys[i + step / 2] == k (or step == 1); the run ends in (i + step / 2, min(i + step, n)]
+  int64_t lo = i + (step >> 1), hi = std::min<int64_t>(i + step, n);  // keys[lo] == k; hi: first index known not in the run
+  while (hi - lo > 1) {
+    const int64_t mid = lo + ((hi - lo) >> 1);
+    if (keys[mid] == k) lo = mid;
+    else hi = mid;
+  }
+  return hi - i;
+}
+
+__device__ __forceinline__ void insert_run(const int64_t *__restrict__ keys, int64_t n, int64_t i, int64_t k,
+                                           JoinEntry *__restrict__ tab, int64_t cap, int32_t *__restrict__ err) {
+  const int64_t len = run_length(keys, n, i, k);
+  const int64_t s = JoinInsert(tab, cap, k, (int32_t)i, (uint32_t)len,
+                               [](uint32_t *w, uint32_t v) { return atomicCAS(w, 0u, v) == 0u; });
+  if (s < 0) atomicCAS(err, 0, (int32_t)E_JOIN_FULL);
+}
+
+__global__ __launch_bounds__(kJoinBlock) void join_build_kernel(const int64_t *__restrict__ keys, const int64_t n,
+                                                                JoinEntry *__restrict__ tab, const int64_t cap,
+                                                                int32_t *__restrict__ err) {
+  const int64_t stride = (int64_t)gridDim.x * kJoinBlock;
+  for (int64_t t = (int64_t)blockIdx.x * kJoinBlock + threadIdx.x; 2 * t < n; t += stride) {
+    const int64_t i0 = 2 * t;
+    const bool both = i0 + 1 < n;
+    int64_t k0, k1;
+    load_pair(keys, i0, both, k0, k1);
+    if (i0 == 0 || keys[i0 - 1] != k0) insert_run(keys, n, i0, k0, tab, cap, err);
+    if (both && k1 != k0) insert_run(keys, n, i0 + 1, k1, tab, cap, err);
+  }
+}
+
+template <typename T>
+__global__ __launch_bounds__(kJoinBlock) void join_probe_count_kernel(const T *__restrict__ col,
+                                                                      const uint64_t *__restrict__ valid, const int64_t n,
+                                                                      const JoinEntry *__restrict__ tab, const int64_t cap,
+                                                                      int64_t *__restrict__ counts,
+                                                                      int32_t *__restrict__ starts,
+                                                                      int32_t *__restrict__ err) {
+  const int64_t stride = (int64_t)gridDim.x * kJoinBlock;
+  for (int64_t t = (int64_t)blockIdx.x * kJoinBlock + threadIdx.x; 2 * t < n; t += stride) {
+    const int64_t i0 = 2 * t;
+    const bool both = i0 + 1 < n;
+    int64_t k[2];
+    load_pair(col, i0, both, k[0], k[1]);
+    int64_t cnt[2] = {0, 0};
+    int32_t st[2] = {0, 0};
+#pragma unroll
+    for (int r = 0; r < 2; r++) {
+      if (r == 1 && !both) break;
+      if (!row_valid(valid, i0 + r)) continue;  // a NULL key matches nothing
+      JoinEntry e;
+      const int64_t s = JoinLookup(tab, cap, k[r], &e);
+      if (s >= 0) {
+        cnt[r] = (int64_t)e.len;
+        st[r] = e.start;
+      } else if (s == kJoinTableFull) {
+        atomicCAS(err, 0, (int32_t)E_JOIN_FULL);
+      }
+    }
+    store_pair(counts, i0, both, cnt[0], cnt[1]);
+    starts[i0] = st[0];
+    if (both) starts[i0 + 1] = st[1];
+  }
+}
+
+// the largest p in [lo, hi) with offs[p] <= j; needs offs[lo] <= j < offs[hi]
+__device__ __forceinline__ int64_t owner_row(const int64_t *__restrict__ offs, int64_t lo, int64_t hi, int64_t j) {
+  while (hi - lo > 1) {
+    const int64_t mid = lo + ((hi - lo) >> 1);
+    if (offs[mid] <= j) lo = mid;
+    else hi = mid;
+  }
+  return lo;
+}
+
+// offs: the n + 1 exclusive offsets of the probe rows' counts (offs[n] ==
+// total); starts: each probe row's run start; build_rows: the build row
+// numbers in sorted-key order.  Output row j belongs to the probe row p with
+// offs[p] <= j < offs[p + 1] and is the (j - offs[p])-th row of p's run.
+__global__ __launch_bounds__(kJoinBlock) void join_expand_kernel(const int64_t *__restrict__ offs,
+                                                                 const int32_t *__restrict__ starts, const int64_t n,
+                                                                 const int64_t total,
+                                                                 const int64_t *__restrict__ build_rows,
+                                                                 int64_t *__restrict__ out_probe,
+                                                                 int64_t *__restrict__ out_build) {
+  __shared__ int64_t s_lo, s_hi;
+  const int64_t ntiles = (total + kExpandTile - 1) / kExpandTile;
+  for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const int64_t j0 = tile * kExpandTile, j1 = std::min<int64_t>(j0 + kExpandTile, total);
+    // the tile's probe rows lie between the owners of its first and last output row
+    if (threadIdx.x == 0) s_lo = owner_row(offs, 0, n, j0);
+    if (threadIdx.x == 64) s_hi = owner_row(offs, 0, n, j1 - 1);
+    __syncthreads();
+    const int64_t j = j0 + 2 * (int64_t)threadIdx.x;
+    if (j < j1) {
+      const bool both = j + 1 < j1;
+      const int64_t p0 = owner_row(offs, s_lo, s_hi + 1, j);
+      int64_t p1 = p0;
+      if (both && j + 1 >= offs[p0 + 1]) p1 = owner_row(offs, p0 + 1, s_hi + 1, j + 1);
+      const int64_t b0 = build_rows[(int64_t)starts[p0] + (j - offs[p0])];
+      const int64_t b1 = both ? build_rows[(int64_t)starts[p1] + (j + 1 - offs[p1])] : b0;
+      store_pair(out_probe, j, both, p0, p1);
+      store_pair(out_build, j, both, b0, b1);
+    }
+    __syncthreads();  // s_lo / s_hi are rewritten by the next tile
+  }
+}
+
+template <typename T>
+void launch_keys(const void *col, int64_t n, int64_t *keys, int64_t *rows, hipStream_t s) {
+  hipLaunchKernelGGL((join_keys_kernel<T>), dim3(PairGrid(n)), dim3(kJoinBlock), 0, s, (const T *)col, n, keys, rows);
+}
+
+template <typename T>
+void launch_probe(const void *col, const uint64_t *valid, int64_t n, const JoinEntry *tab, int64_t cap, int64_t *counts,
+                  int32_t *starts, int32_t *err, hipStream_t s) {
+  hipLaunchKernelGGL((join_probe_count_kernel<T>), dim3(PairGrid(n)), dim3(kJoinBlock), 0, s, (const T *)col, valid, n,
+                     tab, cap, counts, starts, err);
+}
+
+void CheckLaunch(const char *what) {
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) throw std::runtime_error(std::string(what) + ": " + hipGetErrorString(e));
+}
+
+}  // namespace
+
+void JoinKeys(const void *col, int phys, int64_t n, int64_t *keys, int64_t *rows, hipStream_t s) {
+  if (n <= 0) return;
+  switch (phys) {
+    case P_U8: launch_keys<uint8_t>(col, n, keys, rows, s); break;
+    case P_I8: launch_keys<int8_t>(col, n, keys, rows, s); break;
+    case P_I16: launch_keys<int16_t>(col, n, keys, rows, s); break;
+    case P_U16: launch_keys<uint16_t>(col, n, keys, rows, s); break;
+    case P_I32: launch_keys<int32_t>(col, n, keys, rows, s); break;
+    case P_U32: launch_keys<uint32_t>(col, n, keys, rows, s); break;
+    case P_I64: launch_keys<int64_t>(col, n, keys, rows, s); break;
+    case P_U64: launch_keys<uint64_t>(col, n, keys, rows, s); break;
+    default: throw std::runtime_error("join_keys: not an integer column");
+  }
+  CheckLaunch("join_keys");
+}
+
+void JoinBuild(const int64_t *sorted_keys, int64_t n, JoinEntry *tab, int64_t cap, int32_t *err, hipStream_t s) {
+  if (n <= 0) return;
+  hipLaunchKernelGGL(join_build_kernel, dim3(PairGrid(n)), dim3(kJoinBlock), 0, s, sorted_keys, n, tab, cap, err);
+  CheckLaunch("join_build");
+}
+
+void JoinProbeCount(const void *col, int phys, const uint64_t *valid, int64_t n, const JoinEntry *tab, int64_t cap,
+                    int64_t *counts, int32_t *starts, int32_t *err, hipStream_t s) {
+  if (n <= 0) return;
+  switch (phys) {
+    case P_U8: launch_probe<uint8_t>(col, valid, n, tab, cap, counts, starts, err, s); break;
+    case P_I8: launch_probe<int8_t>(col, valid, n, tab, cap, counts, starts, err, s); break;
+    case P_I16: launch_probe<int16_t>(col, valid, n, tab, cap, counts, starts, err, s); break;
+    case P_U16: launch_probe<uint16_t>(col, valid, n, tab, cap, counts, starts, err, s); break;
+    case P_I32: launch_probe<int32_t>(col, valid, n, tab, cap, counts, starts, err, s); break;
+    case P_U32: launch_probe<uint32_t>(col, valid, n, tab, cap, counts, starts, err, s); break;
+    case P_I64: launch_probe<int64_t>(col, valid, n, tab, cap, counts, starts, err, s); break;
+    case P_U64: launch_probe<uint64_t>(col, valid, n, tab, cap, counts, starts, err, s); break;
+    default: throw std::runtime_error("join_probe_count: not an integer column");
+  }
+  CheckLaunch("join_probe_count");
+}
+
+void JoinExpand(const int64_t *offsets, const int32_t *starts, int64_t n, int64_t total, const int64_t *build_rows,
+                int64_t *out_probe, int64_t *out_build, hipStream_t s) {
+  if (n <= 0 || total <= 0) return;
+  const int64_t ntiles = (total + kExpandTile - 1) / kExpandTile;
+  const int grid = (int)std::min<int64_t>(ntiles, (int64_t)NumCUs() * kJoinBlocksPerCU);
+  hipLaunchKernelGGL(join_expand_kernel, dim3(grid), dim3(kJoinBlock), 0, s, offsets, starts, n, total, build_rows,
+                     out_probe, out_build);
+  CheckLaunch("join_expand");
+}
+
+}  // namespace dev
+}  // namespace mbx

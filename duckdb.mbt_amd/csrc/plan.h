@@ -45,7 +45,7 @@ struct AggSpec {
 struct Table;  // engine.h
 
 struct BoundSource {
-  enum Kind { ONE_ROW, RANGE, TABLE, VALUES, SUBQUERY } kind = ONE_ROW;
+  enum Kind { ONE_ROW, RANGE, TABLE, VALUES, SUBQUERY, JOIN } kind = ONE_ROW;
   int64_t range_start = 0, range_stop = 0, range_step = 1;
   bool range_inclusive = false;
   std::shared_ptr<Table> table;
@@ -54,6 +54,13 @@ struct BoundSource {
   std::vector<LogicalType> col_types;
   std::vector<std::string> col_names;
   std::string alias;
+  // JOIN (inner equi-join): col_types / col_names are the left input's, then
+  // the right input's.  left_key reads the left input's columns, right_key the
+  // right input's, both cast to key_type (an integer of at most 8 bytes);
+  // residual (may be null) is every other conjunct of ON, over the joined columns.
+  std::shared_ptr<BoundSource> left, right;
+  BExprPtr left_key, right_key, residual;
+  LogicalType key_type;
   int64_t RangeCount() const;
 };
 

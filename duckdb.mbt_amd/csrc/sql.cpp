@@ -424,7 +424,16 @@ class Parser {
     } while (AcceptOp(","));
   }
 
+  // NATURAL / FULL / SEMI / ANTI are not reserved: in front of JOIN (or FULL
+  // OUTER) they are the join's form, anywhere else a name
+  bool IsJoinWord() const {
+    if (!(IsKw("natural") || IsKw("full") || IsKw("semi") || IsKw("anti"))) return false;
+    const Tok &n = t_[std::min(p_ + 1, t_.size() - 1)];
+    return n.k == Tok::IDENT && (n.s == "join" || n.s == "outer" || n.s == "inner" || n.s == "left" || n.s == "right" || n.s == "full");
+  }
+
   void ParseAlias(TableRef *tr) {
+    if (IsJoinWord()) return;
     if (AcceptKw("as") || Cur().k == Tok::QIDENT || (Cur().k == Tok::IDENT && !IsReserved(Cur().s))) {
       tr->alias = Ident();
       if (AcceptOp("(")) {
@@ -435,7 +444,8 @@ class Parser {
     }
   }
 
-  void ParseFrom(TableRef *tr) {
+  // one input of a FROM clause: a table, a table function, (VALUES ...) or a subquery
+  void ParseFromItem(TableRef *tr) {
     if (AcceptOp("(")) {
       if (AcceptKw("values")) {
         tr->kind = TableRef::VALUES;
@@ -466,8 +476,45 @@ class Parser {
       }
       ParseAlias(tr);
     }
-    if (IsOp(",") || IsKw("join") || IsKw("inner") || IsKw("left") || IsKw("cross"))
-      ThrowError("Not implemented", "joins are not supported by the MI355X backend");
+  }
+
+  // the join forms the backend refuses, each by its name
+  void RefuseJoinForm() {
+    auto no = [](const std::string &what) {
+      ThrowError("Not implemented", what + " is not supported by the MI355X backend (inner JOIN ... ON only)");
+    };
+    if (IsOp(",")) no("a comma join (FROM a, b)");
+    const bool to_join = Peek().k == Tok::IDENT && (Peek().s == "join" || Peek().s == "outer");
+    if (IsKw("left") || IsKw("right") || IsKw("cross")) {
+      std::string w = Cur().s;
+      for (auto &ch : w) ch = (char)toupper((unsigned char)ch);
+      no(w + " JOIN");
+    }
+    if (to_join && IsKw("full")) no("FULL JOIN");
+    if (to_join && IsKw("semi")) no("SEMI JOIN");
+    if (to_join && IsKw("anti")) no("ANTI JOIN");
+    if (IsKw("natural")) no("NATURAL JOIN");
+  }
+
+  // item {[INNER] JOIN item ON cond}*, left-associative
+  void ParseFrom(TableRef *tr) {
+    ParseFromItem(tr);
+    for (;;) {
+      RefuseJoinForm();
+      if (IsKw("inner") && Peek().k == Tok::IDENT && Peek().s == "join") p_++;
+      if (!AcceptKw("join")) break;
+      auto left = std::make_shared<TableRef>(*tr), right = std::make_shared<TableRef>();
+      ParseFromItem(right.get());
+      if (IsKw("using"))
+        ThrowError("Not implemented", "JOIN ... USING (...) is not supported by the MI355X backend (write the ON condition)");
+      ExpectKw("on");
+      TableRef j;
+      j.kind = TableRef::JOIN;
+      j.left = left;
+      j.right = right;
+      j.on = ParseExpr();
+      *tr = j;
+    }
   }
 
   // ---- expressions ---------------------------------------------------------

@@ -4,8 +4,8 @@
 // (/root/reference/src/duckdb_native.c:142-172 duckdb_mb_query -> duckdb_query).
 // This parser covers the statements the reference's tests and the benchmark
 // configurations issue: SELECT [DISTINCT] ... FROM {table | range(..) [tbl(col)]
-// | (VALUES ..) t(cols) | (subquery)} [WHERE] [GROUP BY] [HAVING] [ORDER BY]
-// [LIMIT/OFFSET] [UNION ALL ...], CREATE TABLE [AS SELECT], INSERT INTO ...
+// | (VALUES ..) t(cols) | (subquery)} {[INNER] JOIN <the same> ON cond}* [WHERE]
+// [GROUP BY] [HAVING] [ORDER BY] [LIMIT/OFFSET] [UNION ALL ...], CREATE TABLE [AS SELECT], INSERT INTO ...
 // VALUES/SELECT, DROP TABLE.
 #pragma once
 
@@ -60,13 +60,16 @@ struct Expr {
 };
 
 struct TableRef {
-  enum Kind { NONE, TABLE, RANGE, VALUES, SUBQUERY } kind = NONE;
+  enum Kind { NONE, TABLE, RANGE, VALUES, SUBQUERY, JOIN } kind = NONE;
   std::string name;  // table name or function name (range / generate_series)
   std::vector<ExprPtr> args;
   std::vector<std::vector<ExprPtr>> rows;
   SelectPtr sub;
   std::string alias;
   std::vector<std::string> col_aliases;
+  // JOIN: left [INNER] JOIN right ON on (left-deep chains: left is the join so far)
+  std::shared_ptr<TableRef> left, right;
+  ExprPtr on;
 };
 
 struct OrderItem {

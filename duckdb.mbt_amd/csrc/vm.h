@@ -94,6 +94,7 @@ enum VmErr : int32_t {
   E_DEC_OVF = 6,
   E_HASH_FULL = 7,
   E_KEY_RANGE = 8,  // a GROUP BY key outside the zone map its slot table was sized from
+  E_JOIN_FULL = 9,  // a join table walk met no empty slot within the capacity (join_plan.h)
 };
 
 namespace dev {
