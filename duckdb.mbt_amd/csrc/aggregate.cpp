@@ -1051,11 +1051,20 @@ static bool ScanAggregate(Engine &e, const DRel &src, const BoundSelect &s, DRel
     if (by_codes && tc->code_planes > 0) {
       const ScanPlanePlan pp =
           PlanScanPlanes(tc->code_planes, (i128)tc->code_base, tc->imax, (int64_t)lo, (int64_t)hi, A != nullptr);
-      ProfScope ps(e, "filter_agg", pp.empty ? 0 : (double)ScanPlaneScanBytes(pp.planes, src.n), src.n);
+      // the column's code histogram answers what the planes would (scan_hist.h)
+      const bool by_hist = e.scan_hist && tc->code_hist && !pp.empty && pp.planes > 0;
+      ProfScope ps(e, "filter_agg",
+                   pp.empty  ? 0
+                   : by_hist ? (double)ScanHistBytes(tc->code_planes)
+                             : (double)ScanPlaneScanBytes(pp.planes, src.n),
+                   src.n);
       if (pp.empty) {
         dev::InitAggStatesCounts(st, 1, cstar, 1, e.stream);  // the zone map rules every row out, as below
       } else if (pp.planes == 0) {
         known_count();  // it lets every row in: no plane is read
+      } else if (by_hist) {
+        npartials = dev::FilterAggHist(tc->code_hist, tc->code_planes, pp.clo, pp.chi, tc->code_base, e.d_partials,
+                                       e.stream);
       } else {
         npartials = dev::FilterAggPlanes(tc->codes, tc->code_planes, pp.planes, pp.ge, pp.le, pp.clo, pp.chi,
                                          tc->code_base, A != nullptr, need_mm, src.n, e.d_partials, e.stream);

@@ -9,6 +9,7 @@
 #include "group_pred_plan.h"
 #include "scan_codes.h"
 #include "scan_planes.h"
+#include "scan_hist.h"
 #include "str_match.h"
 #include "vm.h"
 
@@ -108,9 +109,14 @@ int FilterAggPlanes(const void *planes, int b, int planes_read, bool ge, bool le
                     int64_t base, bool sum, bool need_minmax, int64_t nrows, AggPartial *partials, hipStream_t s);
 // Rebuilds from the values of a P_I32 / P_I64 column every word of every plane
 // that holds a row of [begin, end) (both buffers 256-B aligned at row 0, the
-// image's with whole segments for `end` rows)
+// image's with whole segments for `end` rows).  With `hist` (1 << b counters of
+// 8 bytes, scan_hist.h) the codes of rows [begin, end) are added to it.
 void ScanEncodePlanes(const void *values, int phys, void *planes, int b, int64_t base, int64_t begin, int64_t end,
-                      hipStream_t s);
+                      void *hist, hipStream_t s);
+// FilterAggPlanes's answer for the passing codes clo .. chi from the column's
+// code histogram: one workgroup, one partial record (returns 1)
+int FilterAggHist(const void *hist, int b, uint32_t clo, uint32_t chi, int64_t base, AggPartial *partials,
+                  hipStream_t s);
 
 // --- fused GROUP BY on a small-range integer key (config C3) -------------
 // key in [kmin, kmin + nk) (the NULL group in slot nk - 1 when the key has

@@ -58,6 +58,15 @@ struct DevColumn {
   int code_fields = 0;  // codes per word (ScanCodeFields), 0: no field image
   int code_planes = 0;  // bits per code (ScanPlaneBits), 0: no plane image
   int64_t code_base = 0, code_rows = 0, code_cap = 0;
+  // code histogram (scan_hist.h) of a column with a plane image, while
+  // mbx_scan_hist is on and the table has mbx_scan_hist_min_rows rows or
+  // more: 1 << code_planes counters of 8 bytes, counter c the
+  // rows of [0, code_rows) with code c.  It shares the image's life: zeroed and
+  // counted again when the image is rebuilt, added to when it is extended or
+  // regrown, gone when it goes.  A range aggregate the plane scan would answer
+  // is answered from it.
+  void *code_hist = nullptr;
+  std::shared_ptr<void> code_hist_owner;
 };
 
 struct Table {
@@ -189,6 +198,14 @@ struct Options {
   // codes of at most 8 bits as bit planes (scan_planes.h), so that a scan
   // reads only the planes its predicate needs
   int64_t scan_codes_planes_min_rows = (int64_t)1 << 24;
+  // "mbx_scan_hist": a column with a plane image also keeps a histogram of its
+  // codes (scan_hist.h), counted at ingest, and the range aggregates the plane
+  // scan serves are answered from it (false: none is built or used)
+  bool scan_hist = true;
+  // "mbx_scan_hist_min_rows": tables below this many rows keep no histogram
+  // (the default is the planes floor's: below it even a scan of every plane
+  // streams in under 2 us, and the query is launch-bound either way)
+  int64_t scan_hist_min_rows = (int64_t)1 << 24;
   // "mbx_join_max_rows": a join whose matches number more than this fails
   // with an Out of Range error before its result is allocated (one accidental
   // near-cross-product must not ask a shared card's pool for hundreds of GB)

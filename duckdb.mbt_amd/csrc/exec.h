@@ -160,8 +160,10 @@ struct Engine {
   // the query), launches that failed to start
   int64_t sr_launches = 0, sr_aborts = 0, sr_launch_failures = 0;
   // the connection's mbx_scan_codes / mbx_scan_codes_min_rows /
-  // mbx_scan_codes_bits_min_rows / mbx_scan_codes_planes_min_rows (set by Eng)
-  bool scan_codes = true;
+  // mbx_scan_codes_bits_min_rows / mbx_scan_codes_planes_min_rows /
+  // mbx_scan_hist / mbx_scan_hist_min_rows (set by Eng)
+  bool scan_codes = true, scan_hist = true;
+  int64_t scan_hist_min_rows = 0;
   int64_t scan_codes_min_rows = 0, scan_codes_bits_min_rows = 0, scan_codes_planes_min_rows = 0;
   bool profile = false;
   std::vector<ProfEvent> events;

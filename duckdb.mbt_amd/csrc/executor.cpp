@@ -127,6 +127,8 @@ Engine &Eng(Connection &c) {
   e.scan_codes_min_rows = c.opts.scan_codes_min_rows;
   e.scan_codes_bits_min_rows = c.opts.scan_codes_bits_min_rows;
   e.scan_codes_planes_min_rows = c.opts.scan_codes_planes_min_rows;
+  e.scan_hist = c.opts.scan_hist;
+  e.scan_hist_min_rows = c.opts.scan_hist_min_rows;
   SettlePending(e);  // a statement never sees a column before its appended stats
   return e;
 }
@@ -144,7 +146,8 @@ DevBufPtr Alloc(Engine &e, size_t bytes, bool zero) {
 
 DCol ColFromTable(const DevColumn &c) {
   DCol d;
-  for (const auto *o : {&c.data_owner, &c.validity_owner, &c.offsets_owner, &c.chars_owner, &c.codes_owner})
+  for (const auto *o : {&c.data_owner, &c.validity_owner, &c.offsets_owner, &c.chars_owner, &c.codes_owner,
+                        &c.code_hist_owner})
     if (*o) d.pins.push_back(*o);
   d.type = c.type;
   d.phys = c.phys;

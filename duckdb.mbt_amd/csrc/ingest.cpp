@@ -113,6 +113,13 @@ static void Grow(Engine &e, DevColumn &c, int64_t nrows_old, int64_t need) {
 // floor, or the bits per code changing, rebuilds the image once, as the other
 // kind where the codes outgrow 8 bits), and a regrown buffer takes over the
 // used whole segments.
+// With mbx_scan_hist a plane image comes with the histogram of its codes
+// (scan_hist.h), counted by the same encode pass over the same rows: this
+// function is the only writer of both, so whatever drops the image (no zone
+// map, NULLs, codes past 8 bits, too few rows, the option off) drops the
+// histogram (as does a table below mbx_scan_hist_min_rows rows), whatever rebuilds it (CREATE OR REPLACE or a first append, a moved
+// imin, other bits per code, the table crossing the planes floor) zeroes and
+// recounts it, and an extended or regrown image adds the appended rows to it.
 void UpdateScanCodes(Engine &e, DevColumn &c, int64_t nrows) {
   int f = 0, pb = 0;
   if (e.scan_codes && nrows > 0 && nrows >= e.scan_codes_min_rows && c.stats_valid && !c.validity &&
@@ -121,6 +128,11 @@ void UpdateScanCodes(Engine &e, DevColumn &c, int64_t nrows) {
     if (f && nrows >= e.scan_codes_planes_min_rows) pb = ScanPlaneBits(c.phys, c.imin, c.imax);
     if (pb) f = 0;
   }
+  const bool hist = pb && e.scan_hist && nrows >= e.scan_hist_min_rows;
+  if (!hist) {  // the histogram goes with the plane image, or with the option
+    c.code_hist = nullptr;
+    c.code_hist_owner.reset();
+  }
   if (!f && !pb) {
     c.codes = nullptr;
     c.codes_owner.reset();
@@ -128,8 +140,11 @@ void UpdateScanCodes(Engine &e, DevColumn &c, int64_t nrows) {
     c.code_base = c.code_rows = c.code_cap = 0;
     return;
   }
+  // (an image that should have a histogram and has none, built while the option
+  // was off or below mbx_scan_hist_min_rows rows, is rebuilt: only a pass over
+  // every row can count it)
   const bool extend = c.codes && c.code_fields == f && c.code_planes == pb && c.code_base == (int64_t)c.imin &&
-                      c.code_rows <= nrows;
+                      c.code_rows <= nrows && (!hist || c.code_hist);
   const int64_t begin = extend ? c.code_rows : 0;
   if (begin == nrows) return;
   if (!extend || c.code_cap < nrows) {
@@ -149,13 +164,20 @@ void UpdateScanCodes(Engine &e, DevColumn &c, int64_t nrows) {
     c.code_planes = pb;
     c.code_base = (int64_t)c.imin;
   }
+  if (hist && !extend) {  // a rebuilt image counts every row again, into 1 << pb zeroed counters
+    void *nh = nullptr;
+    HIPCHK(hipMalloc(&nh, (size_t)ScanHistBytes(pb)));
+    c.code_hist_owner = DevOwned(e, nh);
+    c.code_hist = nh;
+    HIPCHK(hipMemsetAsync(nh, 0, (size_t)ScanHistBytes(pb), e.stream));
+  }
   if (pb) {
     const int64_t first = begin / 32 * 32;  // the first row of the first rebuilt word of every plane
     ProfScope ps(e, "scan_encode",
                  (double)(nrows - first) * PhysSize(c.phys) +
                      (double)(ScanPlaneScanBytes(pb, nrows) - ScanPlaneScanBytes(pb, first)),
                  nrows - first);
-    dev::ScanEncodePlanes(c.data, c.phys, c.codes, pb, c.code_base, begin, nrows, e.stream);
+    dev::ScanEncodePlanes(c.data, c.phys, c.codes, pb, c.code_base, begin, nrows, c.code_hist, e.stream);
   } else {
     const int64_t first = begin / f * f;  // the first row of the first rebuilt word
     ProfScope ps(e, "scan_encode",

@@ -910,12 +910,32 @@ __global__ __launch_bounds__(256) void filter_agg_planes_kernel(const uint32_t *
 // ((d >> j) & 0x01010101) to bits 24 .. 27.  So a block owns whole words, the
 // 256 threads store 1 KiB of each plane side by side, and a piece lands at
 // ScanPlanePieceByte whichever segment it is in.
-template <typename T>
+// HIST: the block also counts the codes it holds into the column's histogram
+// (scan_hist.h), rows [begin, end) only: the word that holds `begin` is
+// rebuilt from its first row, and the rows of it before `begin` were counted
+// when they came in; the padding past `end` never counts.  Thread t adds the
+// codes of its word to a 32-bit LDS table, kept in kScanHistRep copies picked
+// by the lane (a constant column would otherwise put all 64 lanes of every add
+// on one address), and when the block's pieces are done thread c adds counter
+// c, where it is not zero, to the global one: at most 256 64-bit atomics a
+// block.  ScanEncodePlanes sizes the grid so that a block never counts 2^32
+// rows.
+#ifndef MBX_SCAN_HIST_REP
+#define MBX_SCAN_HIST_REP 8
+#endif
+constexpr int kScanHistRep = MBX_SCAN_HIST_REP;  // a power of two, at most 64
+constexpr int64_t kScanHistBlockPieces = (int64_t)1 << 18;  // pieces a block may count: 2^31 rows
+template <typename T, bool HIST>
 __global__ __launch_bounds__(256) void scan_encode_planes_kernel(const T *__restrict__ v, uint32_t *__restrict__ planes,
-                                                                 int b, int64_t begin, int64_t end, uint64_t base) {
+                                                                 int b, int64_t begin, int64_t end, uint64_t base,
+                                                                 unsigned long long *__restrict__ hist) {
   constexpr int R = 16 / (int)sizeof(T);                   // rows per 16-byte load
   constexpr int UNITS = (int)kScanPlanePieceRows / R;      // 16-byte loads per piece
   __shared__ __attribute__((aligned(16))) uint8_t lds[kScanPlanePieceRows];
+  __shared__ uint32_t tab[HIST ? 256 * kScanHistRep : 1];
+  if (HIST) {
+    for (int i = threadIdx.x; i < 256 * kScanHistRep; i += 256) tab[i] = 0;  // the piece loop's first barrier orders it
+  }
   const int64_t w0 = begin / 32;
   const int64_t q0 = begin / kScanPlanePieceRows, q1 = (end + kScanPlanePieceRows - 1) / kScanPlanePieceRows;
   for (int64_t q = q0 + blockIdx.x; q < q1; q += gridDim.x) {
@@ -956,8 +976,55 @@ __global__ __launch_bounds__(256) void scan_encode_planes_kernel(const T *__rest
         for (int i = 0; i < 8; i++) o |= ((((d[i] >> j) & 0x01010101u) * 0x01020408u) >> 24) << (4 * i);
         planes[ScanPlaneWord(b, k, row)] = o;
       }
+      if (HIST) {
+        uint32_t *mine = tab + (threadIdx.x & (kScanHistRep - 1));
+        if (row >= begin && row + 32 <= end) {
+#pragma unroll
+          for (int i = 0; i < 32; i++) atomicAdd(mine + ((d[i >> 2] >> (8 * (i & 3))) & 0xFFu) * kScanHistRep, 1u);
+        } else {
+          for (int i = 0; i < 32; i++)
+            if (row + i >= begin && row + i < end) atomicAdd(mine + ((d[i >> 2] >> (8 * (i & 3))) & 0xFFu) * kScanHistRep, 1u);
+        }
+      }
     }
     __syncthreads();
+  }
+  if (HIST) {
+    __syncthreads();
+    if ((int)threadIdx.x < (1 << b)) {
+      unsigned long long t = 0;
+#pragma unroll
+      for (int r = 0; r < kScanHistRep; r++) t += tab[threadIdx.x * kScanHistRep + r];
+      if (t) atomicAdd(hist + threadIdx.x, t);
+    }
+  }
+}
+
+// The plane scan's answer from the column's code histogram (scan_hist.h): one
+// block, thread c folds counter c under clo <= c <= chi into the values of an
+// accumulator, and the block reduction and the one partial record are those
+// the scans end with.
+__global__ __launch_bounds__(256) void filter_agg_hist_kernel(const unsigned long long *__restrict__ hist, int b,
+                                                              uint32_t clo, uint32_t chi, int64_t base,
+                                                              AggPartial *partials) {
+  __shared__ Acc part[4];
+  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const uint32_t c = threadIdx.x;
+  const ScanHistValues hv =
+      ScanHistValuesOf(c < (uint32_t)ScanHistBins(b) ? ScanHistBin(c, hist[c], clo, chi) : ScanHistNone(), base);
+  Acc A;
+  A.cnt = hv.cnt;
+  A.slo = hv.slo;
+  A.shi = hv.shi;
+  A.mn = hv.mn;
+  A.mx = hv.mx;
+  acc_wave_reduce(A);
+  if (lane == 0) part[w] = A;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    Acc T0 = part[0];
+    for (int i = 1; i < 4; i++) acc_merge(T0, part[i]);
+    partials[0] = AggPartial{T0.cnt, T0.slo, T0.shi, T0.mn, T0.mx};
   }
 }
 
@@ -1457,17 +1524,36 @@ int FilterAggPlanes(const void *planes, int b, int planes_read, bool ge, bool le
   return grid;
 }
 
+int FilterAggHist(const void *hist, int b, uint32_t clo, uint32_t chi, int64_t base, AggPartial *partials,
+                  hipStream_t s) {
+  if (!hist || b < 1 || b > kScanPlaneMaxBits)
+    throw std::runtime_error("FilterAggHist: no histogram of " + std::to_string(b) + "-bit codes");
+  hipLaunchKernelGGL(filter_agg_hist_kernel, dim3(1), dim3(256), 0, s, (const unsigned long long *)hist, b, clo, chi,
+                     base, partials);
+  CHECK_LAUNCH();
+  return 1;
+}
+
 void ScanEncodePlanes(const void *values, int phys, void *planes, int b, int64_t base, int64_t begin, int64_t end,
-                      hipStream_t s) {
+                      void *hist, hipStream_t s) {
   if (end <= begin) return;
+  if (b < 1 || b > kScanPlaneMaxBits || (phys != P_I64 && phys != P_I32))
+    throw std::runtime_error("ScanEncodePlanes: no kernel for " + std::to_string(b) + "-bit codes of this column");
   const int64_t pieces = (end + kScanPlanePieceRows - 1) / kScanPlanePieceRows - begin / kScanPlanePieceRows;
-  const int grid = (int)std::min<int64_t>(pieces, (int64_t)NumCUs() * 8);
-  if (phys == P_I64)
-    hipLaunchKernelGGL((scan_encode_planes_kernel<int64_t>), dim3(grid), dim3(256), 0, s, (const int64_t *)values,
-                       (uint32_t *)planes, b, begin, end, (uint64_t)base);
-  else
-    hipLaunchKernelGGL((scan_encode_planes_kernel<int32_t>), dim3(grid), dim3(256), 0, s, (const int32_t *)values,
-                       (uint32_t *)planes, b, begin, end, (uint64_t)base);
+  int grid = (int)std::min<int64_t>(pieces, (int64_t)NumCUs() * 8);
+  // a block's 32-bit histogram table counts at most kScanHistBlockPieces pieces
+  if (hist && pieces > grid * kScanHistBlockPieces) grid = (int)((pieces + kScanHistBlockPieces - 1) / kScanHistBlockPieces);
+#define SEP(T, HIST)                                                                                        \
+  hipLaunchKernelGGL((scan_encode_planes_kernel<T, HIST>), dim3(grid), dim3(256), 0, s, (const T *)values, \
+                     (uint32_t *)planes, b, begin, end, (uint64_t)base, (unsigned long long *)hist)
+  if (phys == P_I64) {
+    if (hist) SEP(int64_t, true);
+    else SEP(int64_t, false);
+  } else {
+    if (hist) SEP(int32_t, true);
+    else SEP(int32_t, false);
+  }
+#undef SEP
   CHECK_LAUNCH();
 }
 

@@ -460,6 +460,12 @@ int32_t duckdb_mb_config_set(duckdb_mb_config *c, moonbit_bytes_t key, moonbit_b
   } else if (kl == "mbx_scan_codes_planes_min_rows") {
     ok = IsInt(v, &x) && x >= 0;
     if (ok) c->opts.scan_codes_planes_min_rows = x;
+  } else if (kl == "mbx_scan_hist") {
+    ok = v == "true" || v == "1" || v == "false" || v == "0";
+    if (ok) c->opts.scan_hist = v == "true" || v == "1";
+  } else if (kl == "mbx_scan_hist_min_rows") {
+    ok = IsInt(v, &x) && x >= 0;
+    if (ok) c->opts.scan_hist_min_rows = x;
   } else if (kl == "mbx_join_max_rows") {
     ok = IsInt(v, &x) && x >= 0;
     if (ok) c->opts.join_max_rows = x;

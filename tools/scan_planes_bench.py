@@ -4,7 +4,9 @@
 read different numbers of bit planes (csrc/scan_planes.h), and of building the
 image.  One process measures one library: run it once per build (the library is
 chosen with DUCKDB_MB_AMD_LIB) and alternate the builds.  GPU only.
-Usage: [LABEL=name] [REPS=n] scan_planes_bench.py [rows]
+Usage: [LABEL=name] [REPS=n] [SCAN_HIST=false] scan_planes_bench.py [rows]
+(SCAN_HIST=false sets mbx_scan_hist: without it a library that keeps code
+histograms answers these statements from them, and the figures are that path's)
 
 Prints one JSON line for the setup: LABEL (what the run calls its build, e.g.
 "parent" or "this build"; default the library's file name), REPS, and for each
@@ -28,6 +30,8 @@ n = int(sys.argv[1]) if len(sys.argv) > 1 else 1_000_000_000
 reps = max(3, int(os.environ.get("REPS", "30")))
 cfg = m.Config.create()
 cfg.set("mbx_profile", "true")
+if os.environ.get("SCAN_HIST"):  # SCAN_HIST=false: the plane scan itself (a library without the option refuses the key)
+    cfg.set("mbx_scan_hist", os.environ["SCAN_HIST"])
 c = m.connect_with_config(cfg).value
 
 label = os.environ.get("LABEL") or os.path.basename(m.LIB_PATH)
