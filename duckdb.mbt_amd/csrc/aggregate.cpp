@@ -13,11 +13,13 @@
 
 namespace mbx {
 
-static dev::EmitAgg EmitFor(const AggSpec &a, VClass in_class, dev::AggState *states, DCol &out) {
+static dev::EmitAgg EmitFor(const AggSpec &a, VClass in_class, dev::AggState *states, DCol &out,
+                            bool wide_minmax = false) {
   dev::EmitAgg ea;
   memset(&ea, 0, sizeof(ea));
   ea.kind = a.kind;
   ea.in_class = in_class;
+  ea.wide_minmax = wide_minmax;
   ea.out_phys = PhysOf(a.type);
   ea.avg_scale = a.arg && a.arg->type.id == T_DECIMAL ? a.arg->type.scale : 0;
   ea.states = states;
@@ -37,6 +39,7 @@ static void DropEmptyValidity(Engine &e, DRel &r) {
 struct EmitIn {
   dev::AggState *states;
   VClass in_class;
+  bool wide_minmax = false;  // the states hold a 128-bit MIN / MAX (GlobalReduce)
 };
 typedef std::function<EmitIn(int)> EmitInOf;
 
@@ -60,7 +63,7 @@ static void EmitAggCols(Engine &e, const BoundSelect &s, int64_t rows, const Emi
   for (int j = 0; j < na; j++) {
     DCol oc = AllocOut(e, s.aggs[j].type, rows, true, false);
     const EmitIn in = in_of(j);
-    D.a[j] = EmitFor(s.aggs[j], in.in_class, in.states, oc);
+    D.a[j] = EmitFor(s.aggs[j], in.in_class, in.states, oc, in.wide_minmax);
     out.cols.push_back(oc);
   }
 }
@@ -77,6 +80,12 @@ static DRel EmitOneRow(Engine &e, const BoundSelect &s, const unsigned long long
   EmitAggCols(e, s, 1, in_of, D, out);
   dev::EmitAggRelation(D, e.stream);
   return out;
+}
+
+DRel EmitGlobalStates(Engine &e, const BoundSelect &s, const unsigned long long *cstar, dev::AggState *states) {
+  return EmitOneRow(e, s, cstar, [&](int j) {
+    return EmitIn{states + j, s.aggs[j].kind == A_COUNT_STAR ? VC_I64 : ClassOf(s.aggs[j].arg->type)};
+  });
 }
 
 // The relation of a GROUP BY on one integer key whose groups are slots (key =
@@ -1270,17 +1279,21 @@ static DRel GlobalReduce(Engine &e, const DRel &tmp, const BoundSelect &s, const
   auto cs = Alloc(e, 8);
   unsigned long long cn = (unsigned long long)tmp.n;
   HIPCHK(hipMemcpyAsync(cs->p, &cn, 8, hipMemcpyHostToDevice, e.stream));
+  std::vector<char> wide(std::max(na, 1), 0);
   for (int j = 0; j < na; j++) {
     if (arg_idx[j] < 0) continue;
     const DCol &c = tmp.cols[arg_idx[j]];
     const void *data;
     int phys;
     ReduceInput(c, s.aggs[j], &data, &phys);
-    ProfScope ps(e, "reduce_column", (double)tmp.n * PhysSize((Phys)phys), tmp.n);
+    wide[j] = (s.aggs[j].kind == A_MIN || s.aggs[j].kind == A_MAX) && (phys == P_I128 || phys == P_U64);
+    ProfScope ps(e, "reduce_column", (double)tmp.n * PhysSize((Phys)phys) * (wide[j] ? 2 : 1), tmp.n);
     dev::ReduceColumn(data, phys, c.validity, tmp.n, (dev::AggState *)sb->p + j, e.stream);
+    // MIN / MAX of a 128-bit value: a second pass over the column for the low word
+    if (wide[j]) dev::ReduceMinMax128(data, phys, c.validity, tmp.n, (dev::AggState *)sb->p + j, e.stream);
   }
   DRel out = EmitOneRow(e, s, (const unsigned long long *)cs->p, [&](int j) {
-    return EmitIn{(dev::AggState *)sb->p + j, arg_idx[j] >= 0 ? ClassOf(tmp.cols[arg_idx[j]].type) : VC_I64};
+    return EmitIn{(dev::AggState *)sb->p + j, arg_idx[j] >= 0 ? ClassOf(tmp.cols[arg_idx[j]].type) : VC_I64, wide[j] != 0};
   });
   HIPCHK(hipStreamSynchronize(e.stream));
   return out;

@@ -14,7 +14,8 @@
 #include "vm.h"
 
 namespace mbx {
-struct JoinEntry;  // join_plan.h
+struct JoinEntry;   // join_plan.h
+struct JoinAggRec;  // join_agg_plan.h
 namespace dev {
 
 // validity[w] = ~nullbits[w] over the words covering n rows (tail bits cleared)
@@ -219,6 +220,9 @@ void PartGroupHashedScratch(int64_t n, int nv, size_t *hist_bytes, size_t *start
 // --- generic aggregation over compacted columns ---------------------------
 // vclass: VC_I64 / VC_I128 / VC_F64 of the input column (phys given)
 void ReduceColumn(const void *col, int phys, const uint64_t *valid, int64_t n, AggState *out, hipStream_t s);
+// After ReduceColumn over a 128-bit column (P_I128, P_U64), which leaves the least / greatest high word
+// in min_i / max_i: the low words of its MIN / MAX into min_f / max_f (EmitAgg::wide_minmax reads the pairs)
+void ReduceMinMax128(const void *col, int phys, const uint64_t *valid, int64_t n, AggState *out, hipStream_t s);
 // min/max of an integer key column (for group planning); writes {min,max,nonnull count}
 void KeyRange(const void *col, int phys, const uint64_t *valid, int64_t n, long long *out3, hipStream_t s);
 // Direct-index grouping: slot = valid ? key - kmin : nslots-1 (NULL group).
@@ -302,7 +306,9 @@ int ReadClockStamps(uint64_t *out, int cap, hipStream_t s);
 // keys[i] = the integer column's row i sign- or zero-extended; rows[i] = i (rows may be null)
 void JoinKeys(const void *col, int phys, int64_t n, int64_t *keys, int64_t *rows, hipStream_t s);
 // sorted_keys: the build keys in sorted order; tab: cap zeroed entries
-void JoinBuild(const int64_t *sorted_keys, int64_t n, JoinEntry *tab, int64_t cap, int32_t *err, hipStream_t s);
+// max_run (optional, zeroed): the length of the longest run of equal keys, where that is above 1
+void JoinBuild(const int64_t *sorted_keys, int64_t n, JoinEntry *tab, int64_t cap, int32_t *err, hipStream_t s,
+               uint32_t *max_run = nullptr);
 // counts[i] = build rows that match probe row i (0 for a NULL key), starts[i] = their run's start
 void JoinProbeCount(const void *col, int phys, const uint64_t *valid, int64_t n, const JoinEntry *tab, int64_t cap,
                     int64_t *counts, int32_t *starts, int32_t *err, hipStream_t s);
@@ -310,6 +316,38 @@ void JoinProbeCount(const void *col, int phys, const uint64_t *valid, int64_t n,
 // numbers in sorted-key order.  Writes the total pairs, probe-row-major, build rows ascending.
 void JoinExpand(const int64_t *offsets, const int32_t *starts, int64_t n, int64_t total, const int64_t *build_rows,
                 int64_t *out_probe, int64_t *out_build, hipStream_t s);
+// The fused probe-and-aggregate of a global aggregate over the join
+// (join_agg_plan.h).  p: a program of three stages over the joined columns --
+// instructions [0, end_residual) the ON clause's residual (result in
+// residual_reg), [end_residual, end_where) the WHERE (where_reg), the rest the
+// aggregate arguments (out_reg / out_class as a fused aggregate program's,
+// out_phys the statistics bits: 1 sum, 2 min / max; out_reg 255: COUNT(*));
+// a register of 255: the stage has no predicate.  A V_LOADCOL whose VmCols slot
+// has its bit in build_mask reads at the pair's build row, any other at its
+// probe row.  Writes one JoinAggRec per workgroup and aggregate into partials
+// ([blocks][p.n_out]) and {the join's pairs, the pairs both predicates keep}
+// into block_counts ([blocks][2]); blocks = JoinProbeAggBlocks(n).
+struct JoinAggArgs {
+  const void *key;  // the probe side's key column
+  int32_t key_phys;
+  int32_t pad;
+  const uint64_t *key_valid;
+  int64_t n;  // probe rows
+  const JoinEntry *tab;
+  int64_t cap;
+  const int64_t *build_rows;  // the build row numbers in sorted-key order
+  int32_t end_residual, end_where;
+  int32_t residual_reg, where_reg;
+  uint32_t build_mask;
+  int32_t pad2;
+};
+int JoinProbeAggBlocks(int64_t n);
+void JoinProbeAgg(const VmProgram &p, const VmCols &cols, const JoinAggArgs &a, JoinAggRec *partials,
+                  unsigned long long *block_counts, int blocks, int32_t *err, hipStream_t s);
+// states[0 .. n_out) <- the blocks' records merged (JoinAggMerge), counts_out[0] = the kept pairs,
+// counts_out[1] = the join's pairs; one workgroup, a fixed merge order
+void JoinAggFold(const JoinAggRec *partials, const unsigned long long *block_counts, int blocks, int n_out,
+                 AggState *states, unsigned long long *counts_out, hipStream_t s);
 
 int NumCUs();
 
@@ -325,6 +363,7 @@ struct EmitAgg {
   int32_t in_class;  // VClass of the aggregated column
   int32_t out_phys;  // Phys of the result column
   int32_t avg_scale; // decimal scale for AVG
+  int32_t wide_minmax;  // MIN / MAX of a 128-bit value: {min_f, min_i} / {max_f, max_i} are its {lo, hi} (ReduceMinMax128)
   AggState *states;  // per slot (null for COUNT_STAR)
   void *out;
   uint32_t *valid;   // zeroed bitmap words

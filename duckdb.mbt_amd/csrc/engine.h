@@ -210,6 +210,14 @@ struct Options {
   // with an Out of Range error before its result is allocated (one accidental
   // near-cross-product must not ask a shared card's pool for hundreds of GB)
   int64_t join_max_rows = 2147483647;
+  // "mbx_join_agg": a global aggregate over a join runs the fused
+  // probe-and-aggregate (join_agg_plan.h), which never writes the pairs
+  // (false: every join is materialised first)
+  bool join_agg = true;
+  // "mbx_join_agg_max_run": build sides whose longest run of equal keys is
+  // longer than this take the materialising path (a tile of the fused kernel
+  // costs as many interpreter passes as its longest run)
+  int64_t join_agg_max_run = 8;
   // "mbx_force_peer" (tests): shards on the same device still exchange row
   // results by peer DMA (hipMemcpyPeerAsync), as distinct devices do
   bool force_peer = false;

@@ -322,8 +322,30 @@ ResultPtr HostConstantSelect(const BoundSelect &s);
 void FinishProfile(Connection &c, Engine &e, double total_ms);
 // ---- aggregate.cpp
 DRel Aggregate(Engine &e, const DRel &src, const BoundSelect &s);
+// the one-row relation of s's aggregates (no GROUP BY) from states[j] and the COUNT(*) word
+DRel EmitGlobalStates(Engine &e, const BoundSelect &s, const unsigned long long *cstar, dev::AggState *states);
 // ---- join.cpp
-DRel JoinRel(Engine &e, Connection &c, const BoundSource &src);
+// A join up to and including its table: both inputs run to relations (ranges
+// made real), the side choice, the probe side's key column, the build side's
+// sorted row numbers and the table of its distinct keys.
+struct JoinPrepared {
+  DRel in[2];             // the left and the right input
+  int b = 1, p = 0;       // which of them builds and which probes
+  bool empty = false;     // an input, or the build side without its NULL keys, has no row: no pair
+  DCol pkey;              // the probe side's key column
+  DevBufPtr rows2, tab;   // build row numbers in sorted-key order; the table (JoinEntry x cap)
+  int64_t nb = 0, cap = 0;
+  DevBufPtr max_run;      // with want_max_run: a device word, the longest run of equal build keys
+};
+JoinPrepared JoinPrepare(Engine &e, Connection &c, const BoundSource &src, bool want_max_run = false);
+// the rest: counts, offsets, the limit, the row numbers of the pairs, the gathers, the residual
+DRel JoinPairs(Engine &e, Connection &c, const BoundSource &src, const JoinPrepared &j);
+DRel JoinRel(Engine &e, Connection &c, const BoundSource &src);  // JoinPairs(JoinPrepare(...))
+// s: an aggregate without GROUP BY whose source is a join.  The aggregate
+// relation (before HAVING and the outputs): from the fused
+// probe-and-aggregate where join_agg_plan.h takes the statement, else from
+// JoinPairs on the same prepared join and Aggregate()
+DRel JoinAggregate(Engine &e, Connection &c, const BoundSelect &s);
 // ---- ingest.cpp
 void UpdateScanCodes(Engine &e, DevColumn &c, int64_t nrows);
 void AppendCast(Engine &e, Table &t, DRel r, const std::vector<int> &col_map);

@@ -1621,6 +1621,9 @@ DRel RunBranch(Engine &e, Connection &c, const BoundSelect &s) {
     }
     return r;
   }
+  // a global aggregate over a join: fused into the probe where it can be (join.cpp)
+  if (s.is_agg && s.groups.empty() && s.src.kind == BoundSource::JOIN)
+    return FilterProject(e, JoinAggregate(e, c, s), s.having, s.outputs);
   DRel src = SourceRel(e, c, s.src);
   if (s.is_agg) {
     DRel agg = Aggregate(e, src, s);

@@ -12,8 +12,17 @@
 // the result, probe-row-major with build rows ascending, and GatherRel fetches
 // the columns of each side.  The ON clause's other conjuncts (the residual)
 // filter the joined relation.  The kernels are join_kernels.hip.
+//
+// JoinPrepare runs a join up to its table, JoinPairs does the rest.  An
+// aggregate without GROUP BY over a join (JoinAggregate) prepares the join and,
+// where join_agg_plan.h takes the statement, never makes the pairs: one kernel
+// probes and interprets the residual, the WHERE and the aggregate arguments per
+// pair (join_probe_agg), one folds the workgroups' records (join_agg_fold).
 #include "exec.h"
+#include "join_agg_plan.h"
 #include "join_plan.h"
+#include "knobs.h"
+#include "vm_compile.h"
 
 namespace mbx {
 
@@ -50,27 +59,33 @@ DRel EmptyJoin(Engine &e, const DRel &l, const DRel &r) {
 
 }  // namespace
 
-DRel JoinRel(Engine &e, Connection &c, const BoundSource &src) {
-  DRel in[2] = {SourceRel(e, c, *src.left), SourceRel(e, c, *src.right)};
-  for (DRel &r : in) {
+JoinPrepared JoinPrepare(Engine &e, Connection &c, const BoundSource &src, bool want_max_run) {
+  JoinPrepared j;
+  j.in[0] = SourceRel(e, c, *src.left);
+  j.in[1] = SourceRel(e, c, *src.right);
+  for (DRel &r : j.in) {
     SettleCount(e, r);
     // the virtual column of a range relation becomes a real one: the gather reads it by row number
     if (r.range) r = FilterProject(e, r, nullptr, AllCols(r));
   }
-  if (in[0].n == 0 || in[1].n == 0) return EmptyJoin(e, in[0], in[1]);
+  if (j.in[0].n == 0 || j.in[1].n == 0) {
+    j.empty = true;
+    return j;
+  }
 
-  const int b = in[0].n < in[1].n ? 0 : 1, p = 1 - b;  // build side: fewer rows, the right input on a tie
-  const DRel &build = in[b], &probe = in[p];
+  j.b = j.in[0].n < j.in[1].n ? 0 : 1, j.p = 1 - j.b;  // build side: fewer rows, the right input on a tie
+  const DRel &build = j.in[j.b], &probe = j.in[j.p];
   if (build.n > kJoinMaxBuildRows || probe.n > kJoinMaxBuildRows)
     ThrowError("Out of Range", "join input of " + std::to_string(std::max(build.n, probe.n)) +
                                    " rows, more than the 2147483647 a join side may have");
-  DCol bkey = KeyColumn(e, build, b == 0 ? src.left_key : src.right_key);
-  const DCol pkey = KeyColumn(e, probe, p == 0 ? src.left_key : src.right_key);
-  if (bkey.phys > P_U64 || pkey.phys > P_U64) ThrowError("Internal", "join key is not stored as an integer");
+  DCol bkey = KeyColumn(e, build, j.b == 0 ? src.left_key : src.right_key);
+  j.pkey = KeyColumn(e, probe, j.p == 0 ? src.left_key : src.right_key);
+  if (bkey.phys > P_U64 || j.pkey.phys > P_U64) ThrowError("Internal", "join key is not stored as an integer");
 
   // build keys as int64 beside their row numbers; NULL keys leave first
   int64_t nb = build.n;
-  auto keys = Alloc(e, nb * 8), keys2 = Alloc(e, nb * 8), rows2 = Alloc(e, nb * 8);
+  auto keys = Alloc(e, nb * 8), keys2 = Alloc(e, nb * 8);
+  j.rows2 = Alloc(e, nb * 8);
   DevBufPtr rows_buf;
   int64_t *rows = nullptr;
   DRel kept;  // owns the filtered key and row columns
@@ -88,7 +103,10 @@ DRel JoinRel(Engine &e, Connection &c, const BoundSource &src) {
     notnull->ch.push_back(ColRef(0, bkey.type));
     kept = FilterProject(e, kr, notnull, AllCols(kr));
     nb = kept.n;
-    if (nb == 0) return EmptyJoin(e, in[0], in[1]);
+    if (nb == 0) {
+      j.empty = true;
+      return j;
+    }
     bkey = kept.cols[0];
     rows = (int64_t *)kept.cols[1].data;
     ProfScope ps(e, "join_keys", (double)nb * (PhysSize(bkey.phys) + 8), nb);
@@ -101,21 +119,33 @@ DRel JoinRel(Engine &e, Connection &c, const BoundSource &src) {
   }
   {
     ProfScope ps(e, "radix_sort", (double)nb * 16 * 2, nb);
-    dev::SortPairs((uint64_t *)keys->p, rows, (uint64_t *)keys2->p, (int64_t *)rows2->p, nb, e.stream);
+    dev::SortPairs((uint64_t *)keys->p, rows, (uint64_t *)keys2->p, (int64_t *)j.rows2->p, nb, e.stream);
   }
-  const int64_t cap = JoinCapacity(nb);
-  auto tab = Alloc(e, (size_t)cap * sizeof(JoinEntry), true);
+  j.nb = nb;
+  j.cap = JoinCapacity(nb);
+  j.tab = Alloc(e, (size_t)j.cap * sizeof(JoinEntry), true);
+  if (want_max_run) j.max_run = Alloc(e, sizeof(uint32_t), true);
   {
-    ProfScope ps(e, "join_build", (double)nb * 8 + (double)cap * sizeof(JoinEntry), nb);
-    dev::JoinBuild((const int64_t *)keys2->p, nb, (JoinEntry *)tab->p, cap, e.d_err, e.stream);
+    ProfScope ps(e, "join_build", (double)nb * 8 + (double)j.cap * sizeof(JoinEntry), nb);
+    dev::JoinBuild((const int64_t *)keys2->p, nb, (JoinEntry *)j.tab->p, j.cap, e.d_err, e.stream,
+                   j.max_run ? (uint32_t *)j.max_run->p : nullptr);
   }
+  return j;
+}
+
+DRel JoinPairs(Engine &e, Connection &c, const BoundSource &src, const JoinPrepared &j) {
+  if (j.empty) return EmptyJoin(e, j.in[0], j.in[1]);
+  const int b = j.b, p = j.p;
+  const DRel &build = j.in[b], &probe = j.in[p];
+  const DCol &pkey = j.pkey;
+  const int64_t cap = j.cap;
 
   // probe: counts, their offsets, the total
   const int64_t np = probe.n;
   auto counts = Alloc(e, np * 8), offs = Alloc(e, (np + 1) * 8), starts = Alloc(e, np * 4);
   {
     ProfScope ps(e, "join_probe_count", (double)np * (PhysSize(pkey.phys) + 12 + sizeof(JoinEntry)), np);
-    dev::JoinProbeCount(pkey.data, pkey.phys, pkey.validity, np, (const JoinEntry *)tab->p, cap, (int64_t *)counts->p,
+    dev::JoinProbeCount(pkey.data, pkey.phys, pkey.validity, np, (const JoinEntry *)j.tab->p, cap, (int64_t *)counts->p,
                         (int32_t *)starts->p, e.d_err, e.stream);
   }
   dev::ScanLengths((const int64_t *)counts->p, (int64_t *)offs->p, np, e.stream);
@@ -123,13 +153,13 @@ DRel JoinRel(Engine &e, Connection &c, const BoundSource &src) {
   CheckError(e);
   if (total > c.opts.join_max_rows)
     ThrowError("Out of Range", "join produces " + std::to_string(total) + " rows, more than mbx_join_max_rows");
-  if (total == 0) return EmptyJoin(e, in[0], in[1]);
+  if (total == 0) return EmptyJoin(e, j.in[0], j.in[1]);
 
   // the result's row numbers on each side, then its columns
   auto pidx = Alloc(e, total * 8), bidx = Alloc(e, total * 8);
   {
     ProfScope ps(e, "join_expand", (double)total * 24 + (double)np * 12, total);
-    dev::JoinExpand((const int64_t *)offs->p, (const int32_t *)starts->p, np, total, (const int64_t *)rows2->p,
+    dev::JoinExpand((const int64_t *)offs->p, (const int32_t *)starts->p, np, total, (const int64_t *)j.rows2->p,
                     (int64_t *)pidx->p, (int64_t *)bidx->p, e.stream);
   }
   DRel side[2];
@@ -148,6 +178,174 @@ DRel JoinRel(Engine &e, Connection &c, const BoundSource &src) {
   out.cols = side[0].cols;
   out.cols.insert(out.cols.end(), side[1].cols.begin(), side[1].cols.end());
   if (src.residual) out = FilterProject(e, out, src.residual, AllCols(out));
+  return out;
+}
+
+DRel JoinRel(Engine &e, Connection &c, const BoundSource &src) { return JoinPairs(e, c, src, JoinPrepare(e, c, src)); }
+
+// ---------------------------------------------------------------------------
+// the fused probe-and-aggregate (join_agg_plan.h)
+// ---------------------------------------------------------------------------
+namespace {
+
+// a VARCHAR value anywhere in the tree: a column, a constant, an argument, an operand of a predicate
+bool HasVarchar(const BExprPtr &x) {
+  if (!x) return false;
+  if (ClassOf(x->type) == VC_STR) return true;
+  for (auto &ch : x->ch)
+    if (HasVarchar(ch)) return true;
+  return false;
+}
+
+// The program of the three stages over `joined` (the left input's columns, then
+// the right one's, in place), or false where the compiler refuses one.
+struct JoinAggProgram {
+  VmProgram P;
+  dev::VmCols cols;
+  int end_residual = 0, end_where = 0, residual_reg = 255, where_reg = 255;
+  uint32_t build_mask = 0;
+  double probe_bytes = 0, build_bytes = 0;  // the referenced columns of each side, per pair
+};
+
+bool CompileJoinAgg(const DRel &joined, size_t nleft, int build_side, const BoundSource &src, const BoundSelect &s,
+                    JoinAggProgram &out) {
+  const int na = (int)s.aggs.size();
+  VmCompiler vc(joined, nullptr);
+  try {
+    if (src.residual) out.residual_reg = vc.Compile(*src.residual);
+    out.end_residual = vc.P.n_ins;
+    if (s.where) out.where_reg = vc.Compile(*s.where);
+    out.end_where = vc.P.n_ins;
+    // the predicates' registers stay allocated: a later stage must not reuse them before they are read
+    for (int j = 0; j < na; j++) {
+      const AggSpec &a = s.aggs[j];
+      if (a.kind == A_COUNT_STAR) {
+        vc.P.out_reg[j] = 255;
+        continue;
+      }
+      vc.P.out_reg[j] = (uint8_t)vc.Compile(*a.arg);
+      vc.P.out_class[j] = (uint8_t)ClassOf(a.arg->type);
+      // statistics the kernel accumulates: bit0 sum (SUM/AVG), bit1 min/max; COUNT only counts
+      vc.P.out_phys[j] = a.kind == A_SUM || a.kind == A_AVG ? 1 : a.kind == A_MIN || a.kind == A_MAX ? 2 : 4;
+    }
+  } catch (std::exception &) {
+    return false;  // the materialising path raises the same error if it applies
+  }
+  vc.P.pred_reg = (uint8_t)out.where_reg;
+  vc.P.pred_ins = (uint8_t)out.end_where;
+  vc.P.n_out = na;
+  vc.P.n_regs = vc.high;
+  out.P = vc.P;
+  out.cols = vc.cols;
+  for (size_t col = 0; col < vc.colmap.size(); col++) {
+    if (vc.colmap[col] < 0) continue;
+    const bool on_build = (col >= nleft) == (build_side == 1);
+    const double bytes = PhysSize(joined.cols[col].phys) + (joined.cols[col].validity ? 1.0 / 8 : 0);
+    if (on_build) out.build_mask |= 1u << vc.colmap[col];
+    (on_build ? out.build_bytes : out.probe_bytes) += bytes;
+  }
+  return true;
+}
+
+}  // namespace
+
+DRel JoinAggregate(Engine &e, Connection &c, const BoundSelect &s) {
+  const BoundSource &src = s.src;
+  const int na = (int)s.aggs.size();
+  JoinAggFacts f;
+  f.enabled = c.opts.join_agg;
+  f.n_aggs = na;
+  f.max_aggs = VM_MAX_OUT;
+  f.max_run_limit = c.opts.join_agg_max_run;
+  f.varchar = HasVarchar(src.residual) || HasVarchar(s.where);
+  for (auto &a : s.aggs) {
+    f.distinct |= a.distinct;
+    f.varchar |= HasVarchar(a.arg);
+    f.minmax_128 |= a.arg && (a.kind == A_MIN || a.kind == A_MAX) && ClassOf(a.arg->type) == VC_I128;
+  }
+  // what the statement itself decides is known before anything runs; the
+  // compiler's verdict and the longest run need the prepared join
+  bool take = JoinAggDecide(f).take;
+  const JoinPrepared j = JoinPrepare(e, c, src, take);
+  take = take && !j.empty;  // no pair: the aggregate over no rows, from the path that has always given it
+  JoinAggProgram prog;
+  if (take) {
+    DRel joined;  // virtual: both inputs' columns where they are, un-gathered
+    joined.cols = j.in[0].cols;
+    joined.cols.insert(joined.cols.end(), j.in[1].cols.begin(), j.in[1].cols.end());
+    joined.n = j.in[j.p].n;
+    f.compile_failed = !CompileJoinAgg(joined, j.in[0].cols.size(), j.b, src, s, prog);
+    // the longest run comes back with the error word of the build
+    HIPCHK(hipMemcpyAsync(e.h_pinned, e.d_err, sizeof(int32_t), hipMemcpyDeviceToHost, e.stream));
+    HIPCHK(hipMemcpyAsync(e.h_pinned + 8, j.max_run->p, sizeof(uint32_t), hipMemcpyDeviceToHost, e.stream));
+    HIPCHK(hipStreamSynchronize(e.stream));
+    int32_t err;
+    uint32_t max_run;
+    memcpy(&err, e.h_pinned, sizeof(err));
+    memcpy(&max_run, e.h_pinned + 8, sizeof(max_run));
+    RaiseDeviceError(e, err);
+    f.max_run = std::max<uint32_t>(max_run, 1);  // runs of one row leave the word alone
+    const JoinAggChoice ch = JoinAggDecide(f);
+    take = ch.take;
+    if (!take && Knob("MBX_JOIN_AGG_DEBUG")) fprintf(stderr, "join_probe_agg declined: %s\n", ch.reason);
+  }
+  if (!take) return Aggregate(e, JoinPairs(e, c, src, j), s);
+
+  const DRel &probe = j.in[j.p];
+  const int blocks = dev::JoinProbeAggBlocks(probe.n);
+  const int nrec = std::max(na, 1);
+  auto partials = Alloc(e, (size_t)blocks * nrec * sizeof(JoinAggRec));
+  auto block_counts = Alloc(e, (size_t)blocks * 2 * 8);
+  auto states = Alloc(e, (size_t)nrec * sizeof(dev::AggState));
+  auto counts = Alloc(e, 2 * 8);
+  dev::JoinAggArgs A;
+  memset(&A, 0, sizeof(A));
+  A.key = j.pkey.data;
+  A.key_phys = j.pkey.phys;
+  A.key_valid = j.pkey.validity;
+  A.n = probe.n;
+  A.tab = (const JoinEntry *)j.tab->p;
+  A.cap = j.cap;
+  A.build_rows = (const int64_t *)j.rows2->p;
+  A.end_residual = prog.end_residual;
+  A.end_where = prog.end_where;
+  A.residual_reg = prog.residual_reg;
+  A.where_reg = prog.where_reg;
+  A.build_mask = prog.build_mask;
+  const double partial_bytes = (double)blocks * (na * sizeof(JoinAggRec) + 16);
+  size_t ev = 0;
+  {
+    // the key and one entry per probe row and the partials; the pairs' share is added once their count is known
+    ProfScope ps(e, "join_probe_agg", (double)probe.n * (PhysSize(j.pkey.phys) + sizeof(JoinEntry)) + partial_bytes,
+                 probe.n);
+    if (ps.on) ev = ps.idx;
+    dev::JoinProbeAgg(prog.P, prog.cols, A, (JoinAggRec *)partials->p, (unsigned long long *)block_counts->p, blocks,
+                      e.d_err, e.stream);
+  }
+  {
+    ProfScope ps(e, "join_agg_fold", partial_bytes + (double)na * sizeof(dev::AggState) + 16, blocks);
+    dev::JoinAggFold((const JoinAggRec *)partials->p, (const unsigned long long *)block_counts->p, blocks, na,
+                     (dev::AggState *)states->p, (unsigned long long *)counts->p, e.stream);
+  }
+  // the pair count and the error word in one copy: the limit is raised before
+  // any expression's error, as where the pairs are materialised, and the error
+  // word is clear after either
+  HIPCHK(hipMemcpyAsync(e.h_pinned, counts->p, 16, hipMemcpyDeviceToHost, e.stream));
+  HIPCHK(hipMemcpyAsync(e.h_pinned + 16, e.d_err, sizeof(int32_t), hipMemcpyDeviceToHost, e.stream));
+  HIPCHK(hipStreamSynchronize(e.stream));
+  uint64_t kept_pairs[2];
+  int32_t err;
+  memcpy(kept_pairs, e.h_pinned, 16);
+  memcpy(&err, e.h_pinned + 16, sizeof(err));
+  const uint64_t pairs = kept_pairs[1];
+  if (e.profile) e.events[ev].bytes += (double)pairs * (8 + prog.probe_bytes + prog.build_bytes);
+  if (pairs > (uint64_t)c.opts.join_max_rows) {
+    if (err) HIPCHK(hipMemsetAsync(e.d_err, 0, sizeof(int32_t), e.stream));
+    ThrowError("Out of Range", "join produces " + std::to_string(pairs) + " rows, more than mbx_join_max_rows");
+  }
+  RaiseDeviceError(e, err);
+  DRel out = EmitGlobalStates(e, s, (const unsigned long long *)counts->p, (dev::AggState *)states->p);
+  HIPCHK(hipStreamSynchronize(e.stream));  // states / count buffers released after the emit
   return out;
 }
 

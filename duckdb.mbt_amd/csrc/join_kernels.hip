@@ -10,6 +10,12 @@
 //   join_expand       per OUTPUT row j in [0, total): the probe row whose
 //                     [offsets[p], offsets[p + 1]) holds j and the build row at
 //                     that place of its run
+//   join_probe_agg    a global aggregate over the join without the pairs: per
+//                     probe row the lookup, then one interpreter pass per build
+//                     row of its run over a program of three stages (residual,
+//                     WHERE, aggregate arguments); per-workgroup partial records
+//   join_agg_fold     the partial records merged in a fixed order into the
+//                     AggState array and the counts the emit reads
 //
 // Every lane owns two consecutive rows, so 8-byte columns move as 16 bytes per
 // lane.  join_expand is laid out by output rows, not by probe rows: a probe
@@ -18,6 +24,7 @@
 // Every table walk is bounded by the capacity (join_plan.h); a walk that runs
 // out raises E_JOIN_FULL in the device error word.
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
 #include <algorithm>
@@ -25,9 +32,13 @@
 #include <string>
 
 #include "device.h"
+#include "join_agg_plan.h"
 #include "join_plan.h"
 #include "phys.h"
+#include "types.h"
 #include "vm.h"
+#include "vm_device.h"
+#include "vm_lds.h"
 
 namespace mbx {
 namespace dev {
@@ -100,8 +111,13 @@ __device__ __forceinline__ int64_t run_length(const int64_t *__restrict__ keys, 
 }
 
 __device__ __forceinline__ void insert_run(const int64_t *__restrict__ keys, int64_t n, int64_t i, int64_t k,
-                                           JoinEntry *__restrict__ tab, int64_t cap, int32_t *__restrict__ err) {
+                                           JoinEntry *__restrict__ tab, int64_t cap, int32_t *__restrict__ err,
+                                           uint32_t *max_run) {
   const int64_t len = run_length(keys, n, i, k);
+  // the longest run, for the fused aggregate's choice (a word still 0 after a build stands for 1):
+  // runs of one row touch nothing, a longer one reads the word with a plain load first, so that
+  // it is not one atomic per key on this one address
+  if (max_run && len > 1 && (uint32_t)len > *max_run) atomicMax(max_run, (uint32_t)len);
   const int64_t s = JoinInsert(tab, cap, k, (int32_t)i, (uint32_t)len,
                                [](uint32_t *w, uint32_t v) { return atomicCAS(w, 0u, v) == 0u; });
   if (s < 0) atomicCAS(err, 0, (int32_t)E_JOIN_FULL);
@@ -109,15 +125,15 @@ __device__ __forceinline__ void insert_run(const int64_t *__restrict__ keys, int
 
 __global__ __launch_bounds__(kJoinBlock) void join_build_kernel(const int64_t *__restrict__ keys, const int64_t n,
                                                                 JoinEntry *__restrict__ tab, const int64_t cap,
-                                                                int32_t *__restrict__ err) {
+                                                                int32_t *__restrict__ err, uint32_t *max_run) {
   const int64_t stride = (int64_t)gridDim.x * kJoinBlock;
   for (int64_t t = (int64_t)blockIdx.x * kJoinBlock + threadIdx.x; 2 * t < n; t += stride) {
     const int64_t i0 = 2 * t;
     const bool both = i0 + 1 < n;
     int64_t k0, k1;
     load_pair(keys, i0, both, k0, k1);
-    if (i0 == 0 || keys[i0 - 1] != k0) insert_run(keys, n, i0, k0, tab, cap, err);
-    if (both && k1 != k0) insert_run(keys, n, i0 + 1, k1, tab, cap, err);
+    if (i0 == 0 || keys[i0 - 1] != k0) insert_run(keys, n, i0, k0, tab, cap, err, max_run);
+    if (both && k1 != k0) insert_run(keys, n, i0 + 1, k1, tab, cap, err, max_run);
   }
 }
 
@@ -198,6 +214,208 @@ __global__ __launch_bounds__(kJoinBlock) void join_expand_kernel(const int64_t *
   }
 }
 
+// ---- the fused probe-and-aggregate ------------------------------------------------------------------
+static_assert(sizeof(JoinAggRec) == sizeof(AggState) && offsetof(JoinAggRec, sum_hi) == offsetof(AggState, sum_hi) &&
+                  offsetof(JoinAggRec, min_i) == offsetof(AggState, min_i) &&
+                  offsetof(JoinAggRec, sum_f) == offsetof(AggState, sum_f) &&
+                  offsetof(JoinAggRec, max_f) == offsetof(AggState, max_f),
+              "join_agg_fold writes JoinAggRec records where the emit reads AggState");
+static_assert(VM_MAX_COLS <= 32, "JoinAggArgs::build_mask has one bit per VmCols slot");
+
+__device__ __forceinline__ uint64_t wave_add(uint64_t v) {
+  for (int d = 32; d >= 1; d >>= 1) v += (uint64_t)__shfl_xor((unsigned long long)v, d);
+  return v;
+}
+
+// One 256-row tile of probe rows per workgroup step.  Every lane looks its
+// key up and keeps its run's start and length; a wave then makes as many
+// interpreter passes as its longest run has rows, lane t active while j <
+// len, its pair (probe row, build_rows[start + j]) living in the LDS register
+// planes only.  A V_LOADCOL of a build-side slot reads at the build row,
+// everything else at the probe row.  `active` narrows after the residual and
+// after the WHERE, so the argument stage raises only for pairs both keep.
+// The waves share nothing inside the loop (the planes are per lane, the
+// accumulators per wave, touched by lane 0 only): no barrier until the end,
+// where the four waves' records merge into the workgroup's partials.
+__global__ __launch_bounds__(kJoinBlock) void join_probe_agg_kernel(VmProgram P, VmCols C, JoinAggArgs A,
+                                                                    JoinAggRec *__restrict__ partials,
+                                                                    unsigned long long *__restrict__ block_counts,
+                                                                    int32_t *err) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char vm_lds[];
+  const VmLds R = vm_regs(vm_lds, P.n_regs);
+  __shared__ JoinAggRec s_acc[kJoinBlock / 64][VM_MAX_OUT];
+  __shared__ unsigned long long s_cnt[kJoinBlock / 64][2];
+  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+  if (lane == 0)
+    for (int o = 0; o < P.n_out; o++) s_acc[w][o] = JoinAggEmpty();
+  LdsRF rf{R, t};
+  uint64_t pairs = 0, kept = 0;
+  const int64_t ntiles = (A.n + VM_TILE - 1) / VM_TILE;
+  for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const int64_t row = tile * VM_TILE + t;
+    int len = 0;
+    int64_t start = 0;
+    if (row < A.n && bit_valid(A.key_valid, row)) {  // a NULL key matches nothing
+      int64_t k, khi;
+      load_phys(A.key, A.key_phys, row, k, khi);
+      JoinEntry e;
+      const int64_t s = JoinLookup(A.tab, A.cap, k, &e);
+      if (s >= 0) {
+        len = (int)e.len;
+        start = e.start;
+      } else if (s == kJoinTableFull) {
+        atomicCAS(err, 0, (int32_t)E_JOIN_FULL);
+      }
+    }
+    pairs += (uint64_t)len;  // counted before the residual: the limit is on the join's own pairs
+    int wmax = len;
+    for (int d = 32; d >= 1; d >>= 1) {
+      const int other = __shfl_xor(wmax, d);
+      wmax = other > wmax ? other : wmax;
+    }
+    for (int j = 0; j < wmax; j++) {
+      bool active = j < len;
+      const int64_t brow = active ? A.build_rows[start + j] : 0;
+      int k = 0;
+#pragma unroll 1
+      for (int stage = 0; stage < 3; stage++) {
+        const int kend = stage == 0 ? A.end_residual : stage == 1 ? A.end_where : P.n_ins;
+        for (; k < kend; k++) {
+          const VmIns I = P.ins[k];
+          const bool bside = I.op == V_LOADCOL && ((A.build_mask >> I.a) & 1u);
+          vm_step(P, C, I.op, I.dst, I.a, I.b, I.c, I.aux, bside ? brow : row, active, 0, 1, rf, err);
+        }
+        const int pr = stage == 0 ? A.residual_reg : stage == 1 ? A.where_reg : 255;
+        if (pr != 255) active = active && !rf.nl(pr) && rf.lo(pr) != 0;
+      }
+      kept += active ? 1u : 0u;
+      for (int o = 0; o < P.n_out; o++) {
+        const int r = P.out_reg[o];
+        if (r == 255) continue;  // COUNT(*): the kept pairs
+        const bool has = active && !rf.nl(r);
+        const uint64_t m = __ballot(has);
+        if (!m) continue;  // wave-uniform
+        const int stats = P.out_phys[o];  // bit 0: sum, bit 1: min / max (COUNT: neither)
+        JoinAggRec b = JoinAggEmpty();
+        b.count = (uint64_t)__popcll(m);
+        if (P.out_class[o] == VC_F64) {
+          const double v = __longlong_as_double(rf.lo(r));
+          if (stats & 1) {
+            double sum = has ? v : 0.0;
+            for (int d = 32; d >= 1; d >>= 1) sum += __shfl_xor(sum, d);
+            b.sum_f = sum;
+          }
+          if (stats & 2) {
+            const uint64_t key = f64_order(v);
+            uint64_t mn = has ? key : ~0ull, mx = has ? key : 0ull;
+            for (int d = 32; d >= 1; d >>= 1) {
+              const uint64_t on = (uint64_t)__shfl_xor((unsigned long long)mn, d);
+              const uint64_t ox = (uint64_t)__shfl_xor((unsigned long long)mx, d);
+              mn = on < mn ? on : mn;
+              mx = ox > mx ? ox : mx;
+            }
+            b.min_f = mn;
+            b.max_f = mx;
+          }
+        } else {
+          // a 64-bit class register's high plane is not its sign: only 128-bit values carry one
+          const int64_t v = rf.lo(r), vh = P.out_class[o] == VC_I128 ? rf.hi(r) : (v >> 63);
+          if (stats & 1) {
+            uint64_t lo = has ? (uint64_t)v : 0, hi = has ? (uint64_t)vh : 0;
+            for (int d = 32; d >= 1; d >>= 1) {
+              const uint64_t ol = (uint64_t)__shfl_xor((unsigned long long)lo, d);
+              const uint64_t oh = (uint64_t)__shfl_xor((unsigned long long)hi, d);
+              const uint64_t nl = lo + ol;
+              hi += oh + (nl < lo ? 1u : 0u);
+              lo = nl;
+            }
+            b.sum_lo = lo;
+            b.sum_hi = (int64_t)hi;
+          }
+          if (stats & 2) {
+            long long mn = has ? v : INT64_MAX, mx = has ? v : INT64_MIN;
+            for (int d = 32; d >= 1; d >>= 1) {
+              const long long on = __shfl_xor(mn, d), ox = __shfl_xor(mx, d);
+              mn = on < mn ? on : mn;
+              mx = ox > mx ? ox : mx;
+            }
+            b.min_i = mn;
+            b.max_i = mx;
+          }
+        }
+        if (lane == 0) JoinAggMerge(s_acc[w][o], b);
+      }
+    }
+  }
+  pairs = wave_add(pairs);
+  kept = wave_add(kept);
+  if (lane == 0) {
+    s_cnt[w][0] = pairs;
+    s_cnt[w][1] = kept;
+  }
+  __syncthreads();
+  if (t < P.n_out) {
+    JoinAggRec a = s_acc[0][t];
+    for (int v = 1; v < kJoinBlock / 64; v++) JoinAggMerge(a, s_acc[v][t]);
+    partials[(size_t)blockIdx.x * P.n_out + t] = a;
+  }
+  if (t < 2) {
+    unsigned long long c = 0;
+    for (int v = 0; v < kJoinBlock / 64; v++) c += s_cnt[v][t];
+    block_counts[(size_t)blockIdx.x * 2 + t] = c;
+  }
+}
+
+// One workgroup: thread t merges the records of blocks t, t + 256, ... in
+// ascending order, then the 256 partial merges fold as a tree whose shape
+// depends on nothing but the block count; a double sum therefore comes out
+// the same for the same grid.  counts_out[0] = kept pairs (the COUNT(*) word
+// of the emit), counts_out[1] = the join's pairs.
+__global__ __launch_bounds__(kJoinBlock) void join_agg_fold_kernel(const JoinAggRec *__restrict__ partials,
+                                                                   const unsigned long long *__restrict__ block_counts,
+                                                                   const int blocks, const int n_out,
+                                                                   JoinAggRec *__restrict__ states,
+                                                                   unsigned long long *__restrict__ counts_out) {
+  __shared__ JoinAggRec s_rec[kJoinBlock];
+  __shared__ unsigned long long s_c[kJoinBlock][2];
+  const int t = threadIdx.x;
+  unsigned long long c0 = 0, c1 = 0;
+  for (int b = t; b < blocks; b += kJoinBlock) {
+    c0 += block_counts[(size_t)b * 2];
+    c1 += block_counts[(size_t)b * 2 + 1];
+  }
+  s_c[t][0] = c0;
+  s_c[t][1] = c1;
+  __syncthreads();
+  for (int h = kJoinBlock / 2; h >= 1; h >>= 1) {
+    if (t < h) {
+      s_c[t][0] += s_c[t + h][0];
+      s_c[t][1] += s_c[t + h][1];
+    }
+    __syncthreads();
+  }
+  if (t == 0) {
+    counts_out[0] = s_c[0][1];
+    counts_out[1] = s_c[0][0];
+  }
+  for (int o = 0; o < n_out; o++) {
+    JoinAggRec a = JoinAggEmpty();
+    for (int b = t; b < blocks; b += kJoinBlock) JoinAggMerge(a, partials[(size_t)b * n_out + o]);
+    s_rec[t] = a;
+    __syncthreads();
+    for (int h = kJoinBlock / 2; h >= 1; h >>= 1) {
+      if (t < h) {
+        JoinAggRec x = s_rec[t];
+        JoinAggMerge(x, s_rec[t + h]);
+        s_rec[t] = x;
+      }
+      __syncthreads();
+    }
+    if (t == 0) states[o] = s_rec[0];
+    __syncthreads();  // s_rec is rewritten by the next aggregate
+  }
+}
+
 template <typename T>
 void launch_keys(const void *col, int64_t n, int64_t *keys, int64_t *rows, hipStream_t s) {
   hipLaunchKernelGGL((join_keys_kernel<T>), dim3(PairGrid(n)), dim3(kJoinBlock), 0, s, (const T *)col, n, keys, rows);
@@ -233,9 +451,11 @@ void JoinKeys(const void *col, int phys, int64_t n, int64_t *keys, int64_t *rows
   CheckLaunch("join_keys");
 }
 
-void JoinBuild(const int64_t *sorted_keys, int64_t n, JoinEntry *tab, int64_t cap, int32_t *err, hipStream_t s) {
+void JoinBuild(const int64_t *sorted_keys, int64_t n, JoinEntry *tab, int64_t cap, int32_t *err, hipStream_t s,
+               uint32_t *max_run) {
   if (n <= 0) return;
-  hipLaunchKernelGGL(join_build_kernel, dim3(PairGrid(n)), dim3(kJoinBlock), 0, s, sorted_keys, n, tab, cap, err);
+  hipLaunchKernelGGL(join_build_kernel, dim3(PairGrid(n)), dim3(kJoinBlock), 0, s, sorted_keys, n, tab, cap, err,
+                     max_run);
   CheckLaunch("join_build");
 }
 
@@ -264,6 +484,27 @@ void JoinExpand(const int64_t *offsets, const int32_t *starts, int64_t n, int64_
   hipLaunchKernelGGL(join_expand_kernel, dim3(grid), dim3(kJoinBlock), 0, s, offsets, starts, n, total, build_rows,
                      out_probe, out_build);
   CheckLaunch("join_expand");
+}
+
+int JoinProbeAggBlocks(int64_t n) {
+  const int64_t ntiles = (n + VM_TILE - 1) / VM_TILE;
+  return (int)std::max<int64_t>(1, std::min<int64_t>(ntiles, (int64_t)NumCUs() * kJoinBlocksPerCU));
+}
+
+void JoinProbeAgg(const VmProgram &p, const VmCols &cols, const JoinAggArgs &a, JoinAggRec *partials,
+                  unsigned long long *block_counts, int blocks, int32_t *err, hipStream_t s) {
+  if (a.key_phys > P_U64) throw std::runtime_error("join_probe_agg: not an integer column");
+  if (blocks != JoinProbeAggBlocks(a.n)) throw std::runtime_error("join_probe_agg: partials sized for another grid");
+  hipLaunchKernelGGL(join_probe_agg_kernel, dim3(blocks), dim3(kJoinBlock), VmLdsBytes(p.n_regs), s, p, cols, a, partials,
+                     block_counts, err);
+  CheckLaunch("join_probe_agg");
+}
+
+void JoinAggFold(const JoinAggRec *partials, const unsigned long long *block_counts, int blocks, int n_out,
+                 AggState *states, unsigned long long *counts_out, hipStream_t s) {
+  hipLaunchKernelGGL(join_agg_fold_kernel, dim3(1), dim3(kJoinBlock), 0, s, partials, block_counts, blocks, n_out,
+                     (JoinAggRec *)states, counts_out);
+  CheckLaunch("join_agg_fold");
 }
 
 }  // namespace dev

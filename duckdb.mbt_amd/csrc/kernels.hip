@@ -52,6 +52,7 @@ __device__ __forceinline__ void clk_stamp(int part) {
 #endif
 #include "vm.h"
 #include "vm_device.h"
+#include "vm_lds.h"
 #include "knobs.h"
 
 namespace mbx {
@@ -91,41 +92,7 @@ static inline int GridFor(int64_t work_items, int per_block, int max_blocks) {
 // ---------------------------------------------------------------------------
 // expression VM (tile interpreter)
 // ---------------------------------------------------------------------------
-// VM register planes [reg][row] in dynamic LDS sized to the program's
-// register count (P.n_regs), not VM_MAX_REGS: short programs leave room for
-// more resident workgroups, i.e. more row loads in flight per CU.
-struct VmLds {
-  int64_t *lo;
-  int64_t *hi;
-  uint8_t *nl;
-};
-__device__ __forceinline__ VmLds vm_regs(unsigned char *base, int n_regs) {
-  VmLds R;
-  R.lo = (int64_t *)base;
-  R.hi = R.lo + (size_t)n_regs * VM_TILE;
-  R.nl = (uint8_t *)(R.hi + (size_t)n_regs * VM_TILE);
-  return R;
-}
-static size_t VmLdsBytes(int n_regs) { return (size_t)(n_regs < 1 ? 1 : n_regs) * VM_TILE * 17; }
-
-
-// LDS-plane register file of the tile interpreter
-struct LdsRF {
-  const VmLds &R;
-  int t;
-  __device__ __forceinline__ int64_t &lo(int i) { return R.lo[i * VM_TILE + t]; }
-  __device__ __forceinline__ int64_t &hi(int i) { return R.hi[i * VM_TILE + t]; }
-  __device__ __forceinline__ uint8_t &nl(int i) { return R.nl[i * VM_TILE + t]; }
-};
-
-__device__ void vm_exec(const VmProgram &P, const VmCols &C, int64_t row, bool active, int64_t rs, int64_t rstep,
-                        const VmLds &R, int t, int32_t *err) {
-  LdsRF rf{R, t};
-  for (int k = 0; k < P.n_ins; k++) {
-    const VmIns I = P.ins[k];
-    vm_step(P, C, I.op, I.dst, I.a, I.b, I.c, I.aux, row, active, rs, rstep, rf, err);
-  }
-}
+// (register planes, LdsRF and vm_exec: vm_lds.h, shared with join_kernels.hip)
 
 __global__ __launch_bounds__(256) void vm_filter_kernel(VmProgram P, VmCols C, int64_t nrows, int64_t rs,
                                                         int64_t rstep, uint64_t *__restrict__ bits,
@@ -2340,6 +2307,9 @@ __global__ __launch_bounds__(256) void reduce_column_kernel(const void *col, int
       uint64_t nlo = A.slo + (uint64_t)lo;
       A.shi += hi + (nlo < A.slo ? 1 : 0);
       A.slo = nlo;
+      // the least and the greatest HIGH word: the first half of a 128-bit MIN / MAX (reduce_minmax128_kernel)
+      A.mn = hi < A.mn ? hi : A.mn;
+      A.mx = hi > A.mx ? hi : A.mx;
     } else {
       acc_add(A, true, lo);
     }
@@ -2380,6 +2350,42 @@ void ReduceColumn(const void *col, int phys, const uint64_t *valid, int64_t n, A
   if (n <= 0) return;
   hipLaunchKernelGGL(reduce_column_kernel, dim3(GridFor(n, 256 * 16, NumCUs() * 4)), dim3(256), 0, s, col, phys, valid,
                      n, out);
+  CHECK_LAUNCH();
+}
+
+// MIN / MAX of a 128-bit column, the second half (no atomic is 128 bits wide):
+// reduce_column_kernel has left the least and the greatest high word in min_i /
+// max_i; among the rows that have that high word the low words order the values,
+// unsigned, and fold into min_f / max_f (which a 128-bit column does not use
+// otherwise, and which InitAggStates leaves at ~0 / 0).
+__global__ __launch_bounds__(256) void reduce_minmax128_kernel(const void *col, int phys, const uint64_t *valid,
+                                                               int64_t n, AggState *st) {
+  const int64_t hmin = st->min_i, hmax = st->max_i;
+  uint64_t mn = ~0ull, mx = 0;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    if (!bit_valid(valid, i)) continue;
+    int64_t lo, hi;
+    load_phys(col, phys, i, lo, hi);
+    if (hi == hmin) mn = (uint64_t)lo < mn ? (uint64_t)lo : mn;
+    if (hi == hmax) mx = (uint64_t)lo > mx ? (uint64_t)lo : mx;
+  }
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) {
+    uint64_t o = shfl_xor_u64(mn, m);
+    mn = o < mn ? o : mn;
+    o = shfl_xor_u64(mx, m);
+    mx = o > mx ? o : mx;
+  }
+  if ((threadIdx.x & 63) == 0) {
+    atomicMin(&st->min_f, (unsigned long long)mn);
+    atomicMax(&st->max_f, (unsigned long long)mx);
+  }
+}
+
+void ReduceMinMax128(const void *col, int phys, const uint64_t *valid, int64_t n, AggState *out, hipStream_t s) {
+  if (n <= 0) return;
+  hipLaunchKernelGGL(reduce_minmax128_kernel, dim3(GridFor(n, 256 * 16, NumCUs() * 4)), dim3(256), 0, s, col, phys,
+                     valid, n, out);
   CHECK_LAUNCH();
 }
 
@@ -2758,6 +2764,7 @@ __device__ __forceinline__ void emit_agg_body(const EmitDesc &D, Acc *part, int6
             case 4: /*MAX*/
               if (!S.count) { valid = false; break; }
               if (A.in_class == VC_F64) lo = __double_as_longlong(f64_unorder(A.kind == 3 ? S.min_f : S.max_f));
+              else if (A.wide_minmax) { lo = (int64_t)(A.kind == 3 ? S.min_f : S.max_f); hi = A.kind == 3 ? S.min_i : S.max_i; }
               else { lo = A.kind == 3 ? S.min_i : S.max_i; hi = lo >> 63; }
               break;
             default: /*AVG*/ {

@@ -469,6 +469,12 @@ int32_t duckdb_mb_config_set(duckdb_mb_config *c, moonbit_bytes_t key, moonbit_b
   } else if (kl == "mbx_join_max_rows") {
     ok = IsInt(v, &x) && x >= 0;
     if (ok) c->opts.join_max_rows = x;
+  } else if (kl == "mbx_join_agg") {
+    ok = v == "true" || v == "false";
+    if (ok) c->opts.join_agg = v == "true";
+  } else if (kl == "mbx_join_agg_max_run") {
+    ok = IsInt(v, &x) && x > 0;
+    if (ok) c->opts.join_agg_max_run = x;
   } else if (kl == "mbx_combine") {
     // rccl_loopback: the test-only stand-in for the collectives (rccl_combine.h)
     ok = v == "host" || v == "rccl" || (v == "rccl_loopback" && mbx::Knob("MBX_EXPERIMENTS"));
