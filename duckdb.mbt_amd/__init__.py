@@ -89,6 +89,7 @@ _sig("duckdb_mbx_link_stats", ctypes.c_void_p)
 _sig("duckdb_mbx_statement_plan_stats", _I, _P, ctypes.POINTER(ctypes.c_int64))
 _sig("duckdb_mbx_shard_stats", _I, _P, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_double))
 _sig("duckdb_mbx_engine_stats", _I, _P, ctypes.POINTER(ctypes.c_int64))
+_sig("duckdb_mbx_result_tail_stats", _I, _P, ctypes.POINTER(ctypes.c_int64))
 _sig("duckdb_mbx_shard_timings", _I, _P, ctypes.POINTER(ctypes.c_double), _I)
 _sig("duckdb_mbx_shard_partial", _P, _P, _I)
 _sig("duckdb_mbx_rccl_stats", _I, _P, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_double))
@@ -629,6 +630,14 @@ class Connection:
         lib.duckdb_mbx_engine_stats(self._h, out)
         return {"select_rounds_launches": out[0], "select_rounds_aborts": out[1],
                 "select_rounds_launch_failures": out[2]}
+
+    def result_tail_stats(self) -> dict:
+        """How small results reached the host (extension): written there by the
+        last kernel of a one-row aggregate (mbx_result_tail), or brought by the
+        copy kernel."""
+        out = (ctypes.c_int64 * 2)()
+        lib.duckdb_mbx_result_tail_stats(self._h, out)
+        return {"tail": out[0], "host_copy": out[1]}
 
     def shard_timings(self) -> list:
         """The last sharded dispatch, per shard (extension): device and the us

@@ -68,17 +68,70 @@ static void EmitAggCols(Engine &e, const BoundSelect &s, int64_t rows, const Emi
   }
 }
 
+// What result_tail.h asks about a statement: own_result is the top-level
+// SELECT of ExecuteSelect, whose relation ToHost takes.
+static StatementShape ShapeOf(const Engine &e, const BoundSelect &s) {
+  StatementShape h;
+  h.own_result = e.defer_count_for == (const void *)&s;
+  h.having = (bool)s.having;
+  h.order_by = !s.order.empty();
+  h.limit = s.limit >= 0;
+  h.offset = s.offset > 0;
+  h.union_all = !s.union_all.empty();
+  for (auto &x : s.outputs) h.computed_output |= x->kind != BExpr::COL;
+  return h;
+}
+
 // The one-row relation of an aggregate without GROUP BY, emitted from the
 // states (and, for the fused scans, the workgroups' partials).
+// launch: what runs the emit (EmitAggRelation unless the caller's own last
+// kernel takes the descriptor).  Where the statement allows
+// (ResultTailDecide), the emit also stores the row in the mapped buffer and the
+// relation says so (DRel::tail), so ToHost has nothing left to copy.
 static DRel EmitOneRow(Engine &e, const BoundSelect &s, const unsigned long long *cstar, const EmitInOf &in_of,
-                       const dev::AggPartial *partials = nullptr, int npartials = 0) {
+                       const dev::AggPartial *partials = nullptr, int npartials = 0,
+                       const std::function<void(const dev::EmitDesc &)> &launch = nullptr) {
   DRel out;
   out.n = 1;
   dev::EmitDesc D = EmitDescOf(cstar, 1);
   D.partials = partials;
   D.npartials = npartials;
   EmitAggCols(e, s, 1, in_of, D, out);
-  dev::EmitAggRelation(D, e.stream);
+  ResultTailFacts f;
+  f.enabled = e.result_tail;
+  f.shape = ShapeOf(e, s);
+  f.grouped = !s.groups.empty();
+  f.ncols = D.nagg;
+  f.max_cols = EMIT_MAX_AGGS;
+  f.mapped_bytes = Engine::kMappedBytes;
+  f.max_segs = HOSTCOPY_MAX;
+  f.no_hostcopy = Knob("MBX_NO_HOSTCOPY");
+  int cell[EMIT_MAX_AGGS];
+  bool has_valid[EMIT_MAX_AGGS];
+  for (int j = 0; j < D.nagg && j < EMIT_MAX_AGGS; j++) {
+    f.varchar |= out.cols[j].phys == P_STR;
+    cell[j] = PhysSize(out.cols[j].phys);
+    has_valid[j] = out.cols[j].validity != nullptr;
+  }
+  auto mark = std::make_shared<ResultTailMark>();
+  if (D.nagg <= EMIT_MAX_AGGS) f.need = ResultBufferLayout((size_t)D.nagg, cell, has_valid, 1, 1, false, mark->off);
+  bool bitmaps = true;  // (the emit writes every aggregate's validity word: AllocOut gave each a bitmap)
+  for (int j = 0; j < D.nagg && j < EMIT_MAX_AGGS; j++) bitmaps &= has_valid[j];
+  if (bitmaps && ResultTailDecide(f).take) {
+    mark->serial = e.tail_serial;
+    mark->ncols = (size_t)D.nagg;
+    for (int j = 0; j < D.nagg; j++) {
+      mark->data[j] = out.cols[j].data;
+      mark->valid[j] = out.cols[j].validity;
+      D.host.out[j] = e.h_mapped + mark->off[j].data_off;
+      D.host.valid[j] = (uint64_t *)(e.h_mapped + mark->off[j].valid_off);
+    }
+    D.host.err_src = e.d_err;
+    D.host.err_dst = (int32_t *)e.h_mapped;
+    out.tail = mark;
+  }
+  if (launch) launch(D);
+  else dev::EmitAggRelation(D, e.stream);
   return out;
 }
 
@@ -665,12 +718,7 @@ static DRel DistinctAggregate(Engine &e, const DRel &src, const BoundSelect &s) 
 // column of the aggregate): its GROUP BY may leave the group count on the
 // device, so the rows and the count come back in one copy (DRel::n_dev).
 static bool CountMayStayOnDevice(const Engine &e, const BoundSelect &s) {
-  if (e.defer_count_for != (const void *)&s || s.having || !s.union_all.empty() || !s.order.empty() ||
-      s.limit >= 0 || s.offset > 0)
-    return false;
-  for (auto &x : s.outputs)
-    if (x->kind != BExpr::COL) return false;
-  return true;
+  return RelationReachesHostUnchanged(ShapeOf(e, s));
 }
 
 // ---- the partitioned GROUP BY (group_part.hip): F3 (dense), F3h (hashed), and
@@ -1032,6 +1080,7 @@ static bool ScanAggregate(Engine &e, const DRel &src, const BoundSelect &s, DRel
   dev::AggState *st = (dev::AggState *)e.d_small;
   unsigned long long *cstar = (unsigned long long *)((char *)e.d_small + 1024);
   int npartials = 0;
+  const EmitInOf in_of = [&](int j) { return EmitIn{s.aggs[j].kind == A_COUNT_STAR ? nullptr : st, VC_I64}; };
   if (empty) dev::InitAggStatesCounts(st, 1, cstar, 1, e.stream);
   if (!empty) {
     const DCol *P = pcol >= 0 ? &src.cols[pcol] : nullptr;
@@ -1052,10 +1101,7 @@ static bool ScanAggregate(Engine &e, const DRel &src, const BoundSelect &s, DRel
     bool need_mm = false;
     for (auto &a : s.aggs) need_mm |= a.kind == A_MIN || a.kind == A_MAX;
     auto known_count = [&]() {  // every row passes and only their number is asked
-      dev::InitAggStatesCounts(st, 1, cstar, 1, e.stream);
-      unsigned long long c = (unsigned long long)src.n;
-      HIPCHK(hipMemcpyAsync(cstar, &c, 8, hipMemcpyHostToDevice, e.stream));
-      HIPCHK(hipStreamSynchronize(e.stream));
+      dev::InitAggStatesCounts(st, 1, cstar, 1, e.stream, (unsigned long long)src.n);
     };
     if (by_codes && tc->code_planes > 0) {
       const ScanPlanePlan pp =
@@ -1072,8 +1118,13 @@ static bool ScanAggregate(Engine &e, const DRel &src, const BoundSelect &s, DRel
       } else if (pp.planes == 0) {
         known_count();  // it lets every row in: no plane is read
       } else if (by_hist) {
-        npartials = dev::FilterAggHist(tc->code_hist, tc->code_planes, pp.clo, pp.chi, tc->code_base, e.d_partials,
-                                       e.stream);
+        // one launch folds the histogram, writes its partial record (the shard
+        // combine reads it) and emits the row from it
+        out = EmitOneRow(e, s, cstar, in_of, e.d_partials, 1, [&](const dev::EmitDesc &D) {
+          dev::FilterAggHist(tc->code_hist, tc->code_planes, pp.clo, pp.chi, tc->code_base, e.d_partials, e.stream,
+                             &D);
+        });
+        return true;
       } else {
         npartials = dev::FilterAggPlanes(tc->codes, tc->code_planes, pp.planes, pp.ge, pp.le, pp.clo, pp.chi,
                                          tc->code_base, A != nullptr, need_mm, src.n, e.d_partials, e.stream);
@@ -1109,9 +1160,7 @@ static bool ScanAggregate(Engine &e, const DRel &src, const BoundSelect &s, DRel
       known_count();
     }
   }
-  out = EmitOneRow(
-      e, s, cstar, [&](int j) { return EmitIn{s.aggs[j].kind == A_COUNT_STAR ? nullptr : st, VC_I64}; }, e.d_partials,
-      npartials);
+  out = EmitOneRow(e, s, cstar, in_of, e.d_partials, npartials);
   return true;
 }
 

@@ -115,9 +115,12 @@ int FilterAggPlanes(const void *planes, int b, int planes_read, bool ge, bool le
 void ScanEncodePlanes(const void *values, int phys, void *planes, int b, int64_t base, int64_t begin, int64_t end,
                       void *hist, hipStream_t s);
 // FilterAggPlanes's answer for the passing codes clo .. chi from the column's
-// code histogram: one workgroup, one partial record (returns 1)
+// code histogram: one workgroup, one partial record (returns 1); with emit
+// (its partials that record), the same launch then writes the one-row relation
+// as EmitAggRelation would
+struct EmitDesc;
 int FilterAggHist(const void *hist, int b, uint32_t clo, uint32_t chi, int64_t base, AggPartial *partials,
-                  hipStream_t s);
+                  hipStream_t s, const EmitDesc *emit = nullptr);
 
 // --- fused GROUP BY on a small-range integer key (config C3) -------------
 // key in [kmin, kmin + nk) (the NULL group in slot nk - 1 when the key has
@@ -232,7 +235,9 @@ void GroupAssign(const void *kcol, int kphys, const uint64_t *kvalid, int64_t km
 void GroupReduceColumn(const int32_t *slot_of_row, const void *col, int phys, const uint64_t *valid, int64_t n,
                        AggState *states, hipStream_t s);
 void InitAggStates(AggState *st, int64_t n, hipStream_t s);
-void InitAggStatesCounts(AggState *st, int64_t n, unsigned long long *cs, int64_t nc, hipStream_t s);
+// st[0 .. n) empty, cs[0 .. nc) = count (a row count the host already knows)
+void InitAggStatesCounts(AggState *st, int64_t n, unsigned long long *cs, int64_t nc, hipStream_t s,
+                         unsigned long long count = 0);
 // Compact non-empty slots into the aggregate relation (index list).
 void CompactSlots(const unsigned long long *count_star, int64_t nslots, int32_t *slot_list, int64_t *n_out,
                   hipStream_t s);
@@ -403,6 +408,18 @@ struct EmitDesc {
   // (states of every aggregate and cstar[0]); emit then runs one workgroup
   const AggPartial *partials;
   int32_t npartials;
+  // optional host tail (result_tail.h), for an emit of exactly one row by one
+  // workgroup: with err_dst set, the lane that stores aggregate j's cell also
+  // stores it to out[j] and the row's 64-bit validity word to valid[j], both in
+  // the engine's coherent mapped buffer, then copies the device error word and
+  // fences at system scope, so the host reads the result after the stream wait
+  // with no copy kernel in between
+  struct {
+    void *out[EMIT_MAX_AGGS];
+    uint64_t *valid[EMIT_MAX_AGGS];
+    const int32_t *err_src;
+    int32_t *err_dst;
+  } host;
 };
 void EmitAggRelation(const EmitDesc &d, hipStream_t s);
 

@@ -206,6 +206,11 @@ struct Options {
   // (the default is the planes floor's: below it even a scan of every plane
   // streams in under 2 us, and the query is launch-bound either way)
   int64_t scan_hist_min_rows = (int64_t)1 << 24;
+  // "mbx_result_tail": the kernel that emits the one row of an aggregate
+  // without GROUP BY also stores it in the host's mapped buffer where that row
+  // is the statement's result (result_tail.h), so no copy kernel follows
+  // (false: every small result is copied by one)
+  bool result_tail = true;
   // "mbx_join_max_rows": a join whose matches number more than this fails
   // with an Out of Range error before its result is allocated (one accidental
   // near-cross-product must not ask a shared card's pool for hundreds of GB)
@@ -377,5 +382,8 @@ std::string RcclSelfTestJson(const std::vector<int> &devs, std::string *err, dou
 // adds this connection's (and its shards') select_rounds counters to out:
 // launches, aborts (a workgroup never scheduled: the two-pass form reran), launch failures
 void EngineCounters(const Connection &c, int64_t out[3]);
+// out[0] += small results read from the emit's host tail, out[1] += small
+// results copied by the copy kernel, over the connection and its shards
+void ResultTailCounters(const Connection &c, int64_t out[2]);
 
 }  // namespace mbx

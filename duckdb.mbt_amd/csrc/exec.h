@@ -15,6 +15,7 @@
 
 #include "device.h"
 #include "engine.h"
+#include "result_tail.h"
 
 namespace mbx {
 #define HIPCHK(x)                                                                            \
@@ -131,9 +132,17 @@ struct Engine {
     h_pinned_bytes = b;
     return true;
   }
-  // coherent pinned buffer for small results, written by host_copy_kernel
+  // coherent pinned buffer for small results, written by host_copy_kernel or,
+  // for a one-row aggregate, by the emit itself (result_tail.h)
   static constexpr size_t kMappedBytes = (size_t)64 << 10;
   uint8_t *h_mapped = nullptr;
+  // mbx_result_tail (set by Eng); the statement count that dates a relation's
+  // ResultTailMark (ExecuteSelect advances it, so no mark outlives its
+  // statement); results ToHost read straight from the emit's host tail, and
+  // results it copied with HostCopy (duckdb_mbx_result_tail_stats)
+  bool result_tail = true;
+  uint64_t tail_serial = 0;
+  int64_t tail_results = 0, hostcopy_results = 0;
   // H2D ingest ring: host rows are copied into a pinned slot while the DMA of
   // the previous slot runs (bulk appender path)
   static constexpr int kStageSlots = 4;
@@ -273,7 +282,20 @@ struct DCol {
   i128 zmin = 0, zmax = 0;
 };
 
+// What the emit of a one-row aggregate already stored in the engine's mapped
+// buffer (EmitDesc::host): the relation's column buffers and where their cells
+// lie.  ToHost trusts it only for exactly these buffers, whole, in the
+// statement that made it.
+struct ResultTailMark {
+  uint64_t serial = 0;  // Engine::tail_serial when it was made
+  size_t ncols = 0;
+  const void *data[EMIT_MAX_AGGS];
+  const void *valid[EMIT_MAX_AGGS];
+  ResultColLayout off[EMIT_MAX_AGGS];
+};
+
 struct DRel {
+  std::shared_ptr<const ResultTailMark> tail;  // column passthroughs keep it; every other operator drops it
   std::vector<DCol> cols;
   int64_t n = 0;
   bool range = false;  // column 0 is the virtual range column

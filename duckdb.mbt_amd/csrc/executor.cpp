@@ -129,6 +129,7 @@ Engine &Eng(Connection &c) {
   e.scan_codes_planes_min_rows = c.opts.scan_codes_planes_min_rows;
   e.scan_hist = c.opts.scan_hist;
   e.scan_hist_min_rows = c.opts.scan_hist_min_rows;
+  e.result_tail = c.opts.result_tail;
   SettlePending(e);  // a statement never sees a column before its appended stats
   return e;
 }
@@ -547,6 +548,7 @@ DRel FilterProject(Engine &e, const DRel &rel, const BExprPtr &pred, const std::
     out.n = n;
     out.n_dev = rel.n_dev;
     out.n_owner = rel.n_owner;
+    out.tail = rel.tail;  // (ToHost compares the columns with it)
     for (auto &x : exprs) out.cols.push_back(rel.cols[x->col]);
     return out;
   }
@@ -1337,14 +1339,19 @@ static ResultPtr ToHostPinned(Engine &e, const DRel &r, const std::vector<std::s
   // mapped copy with the n rows, which are trimmed to it (nullptr when that copy
   // does not apply, before anything is launched)
   if (count_dev && (start != 0 || (text && n >= kTextRows))) return nullptr;
-  size_t need = count_dev ? 128 : 64;
   const int64_t w0 = start >> 6, w1 = (start + n + 63) >> 6;
+  std::vector<int> cell(ncols);
+  std::unique_ptr<bool[]> has_valid(new bool[ncols ? ncols : 1]);
+  std::vector<ResultColLayout> lay(ncols);
   for (size_t c = 0; c < ncols; c++) {
     const DCol &d = r.cols[c];
     if (d.phys == P_STR) return nullptr;
-    need += ((size_t)n * PhysSize(d.phys) + 63) & ~(size_t)63;
-    if (d.validity) need += ((size_t)(w1 - w0) * 8 + 63) & ~(size_t)63;
+    cell[c] = PhysSize(d.phys);
+    has_valid[c] = d.validity != nullptr;
   }
+  const size_t cols_end =
+      ResultBufferLayout(ncols, cell.data(), has_valid.get(), n, w1 - w0, count_dev != nullptr, lay.data());
+  size_t need = cols_end;
   // device text: per eligible column, lengths and an exclusive scan (the
   // totals read back with one synchronisation), then the text itself
   struct TextJob {
@@ -1386,8 +1393,15 @@ static ResultPtr ToHostPinned(Engine &e, const DRel &r, const std::vector<std::s
   }
   // small results: one copy kernel into the coherent mapped buffer instead of
   // one DMA per buffer; larger ones: DMA into the (growable) pinned arena
-  const bool mapped = tj.empty() && need <= Engine::kMappedBytes && ncols * 2 + 1 <= HOSTCOPY_MAX &&
-                      !Knob("MBX_NO_HOSTCOPY");
+  const bool mapped =
+      tj.empty() && ResultFitsMapped(need, ncols, Engine::kMappedBytes, HOSTCOPY_MAX, Knob("MBX_NO_HOSTCOPY"));
+  // the emit of a one-row aggregate already stored this very relation, whole,
+  // in the mapped buffer (EmitOneRow): nothing is left to copy
+  bool tail = mapped && r.tail && r.tail->serial == e.tail_serial && r.tail->ncols == ncols && start == 0 && n == 1 &&
+              !count_dev;
+  for (size_t c = 0; tail && c < ncols; c++)
+    tail = r.cols[c].data == r.tail->data[c] && r.cols[c].validity == r.tail->valid[c] &&
+           lay[c].data_off == r.tail->off[c].data_off && lay[c].valid_off == r.tail->off[c].valid_off;
   if (count_dev && !mapped) return nullptr;
   if (!mapped && !e.EnsurePinned(need)) return nullptr;
   uint8_t *const H = mapped ? e.h_mapped : e.h_pinned;
@@ -1403,32 +1417,26 @@ static ResultPtr ToHostPinned(Engine &e, const DRel &r, const std::vector<std::s
     if (mapped) hd.seg[hd.nseg++] = dev::HostCopySeg{src, H + off, (int64_t)bytes};
     else HIPCHK(hipMemcpyAsync(H + off, src, bytes, hipMemcpyDeviceToHost, e.stream));
   };
-  size_t at = 64;  // [0, 4): error word; [64, 72): the device row count (count_dev)
+  // [0, 4): error word; [64, 72): the device row count (count_dev); then the columns (result_tail.h)
   if (!mapped) HIPCHK(hipMemcpyAsync(H, e.d_err, 4, hipMemcpyDeviceToHost, e.stream));
-  if (count_dev) {
-    seg(count_dev, at, 8);
-    at += 64;
-  }
+  if (count_dev) seg(count_dev, 64, 8);
   for (size_t c = 0; c < ncols; c++) {
     const DCol &d = r.cols[c];
     const int sz = PhysSize(d.phys);
     size_t bytes = (size_t)n * sz;
-    data_off[c] = at;
+    data_off[c] = lay[c].data_off;
+    valid_off[c] = lay[c].valid_off;
+    if (tail) continue;
     if (bytes && direct) {
       dcols[c].data.resize(bytes);  // (ResultAlloc: no zero fill)
       HIPCHK(hipMemcpyAsync(dcols[c].data.data(), (const char *)d.data + (size_t)start * sz, bytes,
                             hipMemcpyDeviceToHost, e.stream));
     } else if (bytes) {
-      seg((const char *)d.data + (size_t)start * sz, at, bytes);
+      seg((const char *)d.data + (size_t)start * sz, data_off[c], bytes);
     }
-    at += (bytes + 63) & ~(size_t)63;
-    if (d.validity) {
-      valid_off[c] = at;
-      size_t vb = (size_t)(w1 - w0) * 8;
-      if (n > 0) seg(d.validity + w0, at, vb);
-      at += (vb + 63) & ~(size_t)63;
-    }
+    if (d.validity && n > 0) seg(d.validity + w0, valid_off[c], (size_t)(w1 - w0) * 8);
   }
+  size_t at = cols_end;
   for (auto &j : tj) {
     j.len_off = at;
     if (direct) {  // the host's 32-bit offsets made on the device, straight into the result
@@ -1450,10 +1458,13 @@ static ResultPtr ToHostPinned(Engine &e, const DRel &r, const std::vector<std::s
     }
     at += ((size_t)j.total + 63) & ~(size_t)63;
   }
-  if (mapped) {
+  if (tail) {
+    e.tail_results++;
+  } else if (mapped) {
     hd.err_src = e.d_err;
     hd.err_dst = (int32_t *)H;
     dev::HostCopy(hd, e.stream);
+    e.hostcopy_results++;
   }
   HIPCHK(hipStreamSynchronize(e.stream));
   int32_t err;
@@ -1814,6 +1825,7 @@ ResultPtr ExecuteSelect(Connection &c, const BoundSelect &s) {
   e.profile = c.opts.profile;
   e.events.clear();
   e.ev_used = 0;
+  e.tail_serial++;  // no ResultTailMark of an earlier statement matches from here on
   if (c.sharded()) {
     if (ResultPtr hr = ShardedAggregateHost(c, s)) {
       double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -1848,6 +1860,7 @@ DeviceResultPtr ExecuteSelectDevice(Connection &c, const BoundSelect &s, StreamS
   e.profile = c.opts.profile;
   e.events.clear();
   e.ev_used = 0;
+  e.tail_serial++;
   auto d = std::make_shared<DeviceResult>();
   d->r = RunSelectDev(e, c, s, true);
   d->names.assign(s.names.begin(), s.names.begin() + VisibleCols(s));
@@ -1975,6 +1988,14 @@ void EngineCounters(const Connection &c, int64_t out[3]) {
     out[2] += c.engine->sr_launch_failures;
   }
   for (auto &sc : c.shards) EngineCounters(*sc, out);
+}
+
+void ResultTailCounters(const Connection &c, int64_t out[2]) {
+  if (c.engine) {
+    out[0] += c.engine->tail_results;
+    out[1] += c.engine->hostcopy_results;
+  }
+  for (auto &sc : c.shards) ResultTailCounters(*sc, out);
 }
 
 void HbmCalibrateConn(Connection &c, int64_t bytes, int iters, double out[8]) {

@@ -970,13 +970,19 @@ __global__ __launch_bounds__(256) void scan_encode_planes_kernel(const T *__rest
 // The plane scan's answer from the column's code histogram (scan_hist.h): one
 // block, thread c folds counter c under clo <= c <= chi into the values of an
 // accumulator, and the block reduction and the one partial record are those
-// the scans end with.
+// the scans end with.  With emit, thread 0 then writes the one-row relation
+// from the accumulator it holds (emit_one_row), where emit_agg_kernel would
+// read the record back in a launch of its own.
+__device__ __forceinline__ void emit_one_row(const EmitDesc &D, const Acc &T0, int32_t err);
 __global__ __launch_bounds__(256) void filter_agg_hist_kernel(const unsigned long long *__restrict__ hist, int b,
                                                               uint32_t clo, uint32_t chi, int64_t base,
-                                                              AggPartial *partials) {
+                                                              AggPartial *partials, EmitDesc D, int emit) {
   __shared__ Acc part[4];
   const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const uint32_t c = threadIdx.x;
+  // (the device error word for the host tail, fetched beside the counters)
+  int32_t err = 0;
+  if (emit && threadIdx.x == 0 && D.host.err_dst) err = *D.host.err_src;
   const ScanHistValues hv =
       ScanHistValuesOf(c < (uint32_t)ScanHistBins(b) ? ScanHistBin(c, hist[c], clo, chi) : ScanHistNone(), base);
   Acc A;
@@ -992,6 +998,7 @@ __global__ __launch_bounds__(256) void filter_agg_hist_kernel(const unsigned lon
     Acc T0 = part[0];
     for (int i = 1; i < 4; i++) acc_merge(T0, part[i]);
     partials[0] = AggPartial{T0.cnt, T0.slo, T0.shi, T0.mn, T0.mx};
+    if (emit) emit_one_row(D, T0, err);
   }
 }
 
@@ -1271,7 +1278,8 @@ __global__ void init_agg_states_kernel(AggState *st, int64_t n) {
   }
 }
 
-__global__ void init_states_counts_kernel(AggState *st, int64_t n, unsigned long long *cs, int64_t nc) {
+__global__ void init_states_counts_kernel(AggState *st, int64_t n, unsigned long long *cs, int64_t nc,
+                                          unsigned long long count) {
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n || i < nc; i += (int64_t)gridDim.x * blockDim.x) {
     if (i < n) {
       AggState z;
@@ -1280,14 +1288,15 @@ __global__ void init_states_counts_kernel(AggState *st, int64_t n, unsigned long
       z.sum_f = 0; z.min_f = 0xFFFFFFFFFFFFFFFFull; z.max_f = 0;
       st[i] = z;
     }
-    if (i < nc) cs[i] = 0;
+    if (i < nc) cs[i] = count;
   }
 }
 
-void InitAggStatesCounts(AggState *st, int64_t n, unsigned long long *cs, int64_t nc, hipStream_t s) {
+void InitAggStatesCounts(AggState *st, int64_t n, unsigned long long *cs, int64_t nc, hipStream_t s,
+                         unsigned long long count) {
   int64_t m = n > nc ? n : nc;
   if (m <= 0) return;
-  hipLaunchKernelGGL(init_states_counts_kernel, dim3(GridFor(m, 256, 1024)), dim3(256), 0, s, st, n, cs, nc);
+  hipLaunchKernelGGL(init_states_counts_kernel, dim3(GridFor(m, 256, 1024)), dim3(256), 0, s, st, n, cs, nc, count);
   CHECK_LAUNCH();
 }
 
@@ -1492,11 +1501,14 @@ int FilterAggPlanes(const void *planes, int b, int planes_read, bool ge, bool le
 }
 
 int FilterAggHist(const void *hist, int b, uint32_t clo, uint32_t chi, int64_t base, AggPartial *partials,
-                  hipStream_t s) {
+                  hipStream_t s, const EmitDesc *emit) {
   if (!hist || b < 1 || b > kScanPlaneMaxBits)
     throw std::runtime_error("FilterAggHist: no histogram of " + std::to_string(b) + "-bit codes");
+  EmitDesc D;
+  if (emit) D = *emit;
+  else memset(&D, 0, sizeof(D));
   hipLaunchKernelGGL(filter_agg_hist_kernel, dim3(1), dim3(256), 0, s, (const unsigned long long *)hist, b, clo, chi,
-                     base, partials);
+                     base, partials, D, emit ? 1 : 0);
   CHECK_LAUNCH();
   return 1;
 }
@@ -2676,9 +2688,83 @@ __global__ void slot_scatter_kernel(const int32_t *flag, const int32_t *pos, int
 // words from a wave ballot (each wave owns 64 consecutive output rows), so the
 // output bitmaps need no zeroing and no atomics.  part: LDS room for one Acc
 // per wave (the partials reduction).
+// The cell {lo, hi} of aggregate A for a slot with cstar rows and state *S
+// (not read for COUNT(*)); false: the cell is NULL.
+__device__ __forceinline__ bool emit_cell(const EmitAgg &A, unsigned long long cstar, const AggState *S, int64_t &lo,
+                                          int64_t &hi) {
+  lo = 0;
+  hi = 0;
+  switch (A.kind) {
+    case 0: /*COUNT_STAR*/ lo = (int64_t)cstar; return true;
+    case 1: /*COUNT*/ lo = (int64_t)S->count; return true;
+    case 2: /*SUM*/
+      if (!S->count) return false;
+      if (A.in_class == VC_F64) lo = __double_as_longlong(S->sum_f);
+      else { lo = (int64_t)S->sum_lo; hi = S->sum_hi; }
+      return true;
+    case 3: /*MIN*/
+    case 4: /*MAX*/
+      if (!S->count) return false;
+      if (A.in_class == VC_F64) lo = __double_as_longlong(f64_unorder(A.kind == 3 ? S->min_f : S->max_f));
+      else if (A.wide_minmax) { lo = (int64_t)(A.kind == 3 ? S->min_f : S->max_f); hi = A.kind == 3 ? S->min_i : S->max_i; }
+      else { lo = A.kind == 3 ? S->min_i : S->max_i; hi = lo >> 63; }
+      return true;
+    default: /*AVG*/ {
+      if (!S->count) return false;
+      double v;
+      if (A.in_class == VC_F64) v = S->sum_f / (double)S->count;
+      else {
+        double sum = i128_to_double(mk128((int64_t)S->sum_lo, S->sum_hi));
+        double div = (double)S->count;
+        for (int k = 0; k < A.avg_scale; k++) div *= 10.0;
+        v = sum / div;
+      }
+      lo = __double_as_longlong(v);
+      return true;
+    }
+  }
+}
+
+// The one-row relation of a fused scan from the accumulator T0 that one thread
+// holds (the scan's partials merged; every aggregate reads the same integer
+// column): slot 0's count and states are written as the shard combine and later
+// readers expect them, and the row is emitted from registers, with no trip
+// through memory in between.  With the host tail (D.host), err is the device
+// error word, read by the caller while it waited for its own loads.
+__device__ __forceinline__ void emit_one_row(const EmitDesc &D, const Acc &T0, int32_t err) {
+  ((unsigned long long *)D.cstar)[0] = T0.cnt;
+  AggState S;
+  S.count = T0.cnt; S.sum_lo = T0.slo; S.sum_hi = T0.shi;
+  S.min_i = T0.mn; S.max_i = T0.mx;
+  S.sum_f = 0; S.min_f = 0xFFFFFFFFFFFFFFFFull; S.max_f = 0;
+  const bool host = D.host.err_dst != nullptr;
+  for (int j = 0; j < D.nagg; j++) {
+    const EmitAgg &A = D.a[j];
+    if (AggState *G = A.states) {
+      G->count = S.count; G->sum_lo = S.sum_lo; G->sum_hi = S.sum_hi;
+      G->min_i = S.min_i; G->max_i = S.max_i;
+    }
+    int64_t lo, hi;
+    const bool valid = emit_cell(A, T0.cnt, &S, lo, hi);
+    store_phys(A.out, A.out_phys, 0, lo, hi);
+    A.valid[0] = valid ? 1u : 0u;
+    if (host) {
+      store_phys(D.host.out[j], A.out_phys, 0, lo, hi);
+      *D.host.valid[j] = valid ? 1ull : 0ull;
+    }
+  }
+  if (host) {
+    *D.host.err_dst = err;
+    __threadfence_system();
+  }
+}
+
 __device__ __forceinline__ void emit_agg_body(const EmitDesc &D, Acc *part, int64_t bid, int64_t nb) {
   if (D.npartials > 0) {
-    // slot 0 from the filter-aggregate's per-workgroup partials (one workgroup)
+    // the one row of a fused scan (EmitOneRow) from its per-workgroup
+    // partials: one workgroup, slot 0, no keys
+    int32_t err = 0;
+    if (threadIdx.x == 0 && D.host.err_dst) err = *D.host.err_src;
     Acc A;
     A.cnt = 0; A.slo = 0; A.shi = 0; A.mn = INT64_MAX; A.mx = INT64_MIN;
     for (int i = threadIdx.x; i < D.npartials; i += blockDim.x) {
@@ -2693,20 +2779,9 @@ __device__ __forceinline__ void emit_agg_body(const EmitDesc &D, Acc *part, int6
     if (threadIdx.x == 0) {
       Acc T0 = part[0];
       for (int i = 1; i < (int)(blockDim.x >> 6); i++) acc_merge(T0, part[i]);
-      unsigned long long *cs = (unsigned long long *)D.cstar;
-      cs[0] = T0.cnt;
-      for (int j = 0; j < D.nagg; j++) {
-        AggState *S = D.a[j].states;
-        if (!S) continue;
-        S->count = T0.cnt;
-        S->sum_lo = T0.slo;
-        S->sum_hi = T0.shi;
-        S->min_i = T0.mn;
-        S->max_i = T0.mx;
-      }
-      __threadfence_block();
+      emit_one_row(D, T0, err);
     }
-    __syncthreads();
+    return;
   }
   const int64_t n = D.slot_list ? *D.n_list : D.nslots;
   const int lane = threadIdx.x & 63;
@@ -2749,48 +2824,25 @@ __device__ __forceinline__ void emit_agg_body(const EmitDesc &D, Acc *part, int6
       bool valid = in;
       int64_t lo = 0, hi = 0;
       if (in) {
-        if (A.kind == 0 /*COUNT_STAR*/) {
-          lo = (int64_t)D.cstar[sl];
-        } else {
-          const AggState &S = A.states[sl];
-          switch (A.kind) {
-            case 1: /*COUNT*/ lo = (int64_t)S.count; break;
-            case 2: /*SUM*/
-              if (!S.count) { valid = false; break; }
-              if (A.in_class == VC_F64) lo = __double_as_longlong(S.sum_f);
-              else { lo = (int64_t)S.sum_lo; hi = S.sum_hi; }
-              break;
-            case 3: /*MIN*/
-            case 4: /*MAX*/
-              if (!S.count) { valid = false; break; }
-              if (A.in_class == VC_F64) lo = __double_as_longlong(f64_unorder(A.kind == 3 ? S.min_f : S.max_f));
-              else if (A.wide_minmax) { lo = (int64_t)(A.kind == 3 ? S.min_f : S.max_f); hi = A.kind == 3 ? S.min_i : S.max_i; }
-              else { lo = A.kind == 3 ? S.min_i : S.max_i; hi = lo >> 63; }
-              break;
-            default: /*AVG*/ {
-              if (!S.count) { valid = false; break; }
-              double v;
-              if (A.in_class == VC_F64) v = S.sum_f / (double)S.count;
-              else {
-                double sum = i128_to_double(mk128((int64_t)S.sum_lo, S.sum_hi));
-                double div = (double)S.count;
-                for (int k = 0; k < A.avg_scale; k++) div *= 10.0;
-                v = sum / div;
-              }
-              lo = __double_as_longlong(v);
-              break;
-            }
-          }
-        }
-        if (valid) store_phys(A.out, A.out_phys, i, lo, hi);
-        else store_phys(A.out, A.out_phys, i, 0, 0);
+        if (A.kind == 0 /*COUNT_STAR*/) valid = emit_cell(A, D.cstar[sl], nullptr, lo, hi);
+        else valid = emit_cell(A, 0, A.states + sl, lo, hi);
+        store_phys(A.out, A.out_phys, i, lo, hi);  // (0 for a NULL cell)
+        if (D.host.err_dst && i == 0) store_phys(D.host.out[j], A.out_phys, 0, lo, hi);
       }
       uint64_t m = __ballot(valid);
       if (lane == 0) {
         A.valid[base >> 5] = (uint32_t)m;
         if (base + 32 < n) A.valid[(base >> 5) + 1] = (uint32_t)(m >> 32);
+        if (D.host.err_dst && base == 0) *D.host.valid[j] = m;
       }
     }
+  }
+  if (D.host.err_dst) {
+    // the host tail: the cells and validity words above went to the mapped
+    // buffer too; the error word follows them (one workgroup, one row: thread 0
+    // stored every one), visible to the host once the stream has drained
+    if (bid == 0 && threadIdx.x == 0) *D.host.err_dst = *D.host.err_src;
+    __threadfence_system();
   }
 }
 
@@ -3214,6 +3266,8 @@ namespace mbx {
 namespace dev {
 
 void EmitAggRelation(const EmitDesc &d, hipStream_t s) {
+  if (d.host.err_dst && (d.nslots != 1 || d.slot_list))
+    throw std::runtime_error("EmitAggRelation: the host tail takes exactly one row");
   hipLaunchKernelGGL(emit_agg_kernel, dim3(d.npartials > 0 ? 1 : GridFor(d.nslots, 256, 1024)), dim3(256), 0, s, d);
   CHECK_LAUNCH();
 }

@@ -466,6 +466,9 @@ int32_t duckdb_mb_config_set(duckdb_mb_config *c, moonbit_bytes_t key, moonbit_b
   } else if (kl == "mbx_scan_hist_min_rows") {
     ok = IsInt(v, &x) && x >= 0;
     if (ok) c->opts.scan_hist_min_rows = x;
+  } else if (kl == "mbx_result_tail") {
+    ok = v == "true" || v == "1" || v == "false" || v == "0";
+    if (ok) c->opts.result_tail = v == "true" || v == "1";
   } else if (kl == "mbx_join_max_rows") {
     ok = IsInt(v, &x) && x >= 0;
     if (ok) c->opts.join_max_rows = x;
@@ -1934,6 +1937,15 @@ int32_t duckdb_mbx_engine_stats(duckdb_mb_connection *h, int64_t *out3) {
   out3[0] = out3[1] = out3[2] = 0;
   EngineCounters(h->conn, out3);
   return 3;
+}
+
+// out2 = {small results the host read from the emit's host tail, small results
+// the copy kernel brought} over the connection and its shards.
+int32_t duckdb_mbx_result_tail_stats(duckdb_mb_connection *h, int64_t *out2) {
+  if (!h || !out2) return 0;
+  out2[0] = out2[1] = 0;
+  ResultTailCounters(h->conn, out2);
+  return 2;
 }
 
 int32_t duckdb_mbx_result_raw(duckdb_mb_result *r, int32_t col, int32_t row, void *out, int32_t out_len) {

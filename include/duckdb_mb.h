@@ -309,6 +309,12 @@ int32_t duckdb_mbx_shard_stats(duckdb_mb_connection *connection, int64_t *out6, 
  * two-pass form ran instead)}.  Returns 3 (0: no handle). */
 int32_t duckdb_mbx_engine_stats(duckdb_mb_connection *connection, int64_t *out3);
 
+/* How small results reached the host, over the connection and its shards:
+ * out2 = {results the last kernel of a one-row aggregate wrote to the host
+ * itself (mbx_result_tail), results a copy kernel brought}.  Returns 2 (0: no
+ * handle). */
+int32_t duckdb_mbx_result_tail_stats(duckdb_mb_connection *connection, int64_t *out2);
+
 /* The last sharded dispatch, per shard i: out[4 i .. 4 i + 3] = {device,
  * wake_us, launch_us, done_us}, us since the dispatch began (the worker took
  * the job; its plan and launches were queued; its result reached the host:
