@@ -286,6 +286,12 @@ static bool DirectReduceAll(Engine &e, const void *kdata, Phys kphys, int64_t km
   return true;
 }
 
+// MIN / MAX of a 128-bit value (UBIGINT: 64 unsigned bits, ordered like one) takes two passes: no atomic
+// is 128 bits wide (ReduceMinMax128, GroupMinMax128); the emit then reads the pairs (EmitAgg::wide_minmax)
+static bool WideMinMax(const AggSpec &a, int phys) {
+  return (a.kind == A_MIN || a.kind == A_MAX) && (phys == P_I128 || phys == P_U64);
+}
+
 // The generic paths work on tmp = [groups..., agg args...] of the filtered
 // source (FilterProject); arg_idx[j] is aggregate j's column in it, -1 for
 // COUNT(*).  A VARCHAR argument is only ever counted: its offsets stand in.
@@ -344,6 +350,7 @@ static DRel HashAggregate(Engine &e, const DRel &tmp, const BoundSelect &s, cons
   std::vector<DevBufPtr> states(na);
   std::vector<DevBufPtr> keep;
   std::vector<dev::AggState *> st_of(na, nullptr);
+  std::vector<char> wide(std::max(na, 1), 0);
   const unsigned long long *cstar = nullptr;
   DevBufPtr cs;
   // few groups: LDS-privatised reduction keyed by the dense group id
@@ -367,9 +374,14 @@ static DRel HashAggregate(Engine &e, const DRel &tmp, const BoundSelect &s, cons
     }
     states[j] = Alloc(e, (size_t)std::max<int64_t>(ngroups, 1) * sizeof(dev::AggState));
     dev::InitAggStates((dev::AggState *)states[j]->p, ngroups, e.stream);
-    ProfScope ps(e, "group_reduce", (double)n * (PhysSize((Phys)phys) + 4), n);
+    wide[j] = WideMinMax(s.aggs[j], phys);
+    ProfScope ps(e, "group_reduce", (double)n * (PhysSize((Phys)phys) + 4) * (wide[j] ? 2 : 1), n);
     dev::GroupReduceColumn((const int32_t *)slot_of->p, data, phys, c.validity, n, (dev::AggState *)states[j]->p,
                            e.stream);
+    // MIN / MAX of a 128-bit value: a second pass over the column for the low words
+    if (wide[j])
+      dev::GroupMinMax128((const int32_t *)slot_of->p, data, phys, c.validity, n, (dev::AggState *)states[j]->p,
+                          e.stream);
     st_of[j] = (dev::AggState *)states[j]->p;
   }
   DRel keys;
@@ -380,7 +392,7 @@ static DRel HashAggregate(Engine &e, const DRel &tmp, const BoundSelect &s, cons
   // (no key in the descriptor: the key columns are the gathered ones)
   dev::EmitDesc D = EmitDescOf(cstar, ngroups);
   EmitAggCols(e, s, ngroups, [&](int j) {
-    return EmitIn{st_of[j], arg_idx[j] >= 0 ? ClassOf(tmp.cols[arg_idx[j]].type) : VC_I64};
+    return EmitIn{st_of[j], arg_idx[j] >= 0 ? ClassOf(tmp.cols[arg_idx[j]].type) : VC_I64, wide[j] != 0};
   }, D, out);
   if (ngroups > 0) dev::EmitAggRelation(D, e.stream);
   HIPCHK(hipStreamSynchronize(e.stream));
@@ -1335,7 +1347,7 @@ static DRel GlobalReduce(Engine &e, const DRel &tmp, const BoundSelect &s, const
     const void *data;
     int phys;
     ReduceInput(c, s.aggs[j], &data, &phys);
-    wide[j] = (s.aggs[j].kind == A_MIN || s.aggs[j].kind == A_MAX) && (phys == P_I128 || phys == P_U64);
+    wide[j] = WideMinMax(s.aggs[j], phys);
     ProfScope ps(e, "reduce_column", (double)tmp.n * PhysSize((Phys)phys) * (wide[j] ? 2 : 1), tmp.n);
     dev::ReduceColumn(data, phys, c.validity, tmp.n, (dev::AggState *)sb->p + j, e.stream);
     // MIN / MAX of a 128-bit value: a second pass over the column for the low word
@@ -1396,6 +1408,7 @@ static bool SlotGroupAggregate(Engine &e, const DRel &tmp, const BoundSelect &s,
   }
   const int na = (int)s.aggs.size();
   std::vector<DevBufPtr> states(na);
+  std::vector<char> wide(std::max(na, 1), 0);
   for (int j = 0; j < na; j++) {
     if (arg_idx[j] < 0) continue;
     const DCol &c = tmp.cols[arg_idx[j]];
@@ -1404,9 +1417,14 @@ static bool SlotGroupAggregate(Engine &e, const DRel &tmp, const BoundSelect &s,
     ReduceInput(c, s.aggs[j], &data, &phys);
     states[j] = Alloc(e, nslots * sizeof(dev::AggState));
     dev::InitAggStates((dev::AggState *)states[j]->p, nslots, e.stream);
-    ProfScope ps(e, "group_reduce", (double)tmp.n * (PhysSize((Phys)phys) + 4), tmp.n);
+    wide[j] = WideMinMax(s.aggs[j], phys);
+    ProfScope ps(e, "group_reduce", (double)tmp.n * (PhysSize((Phys)phys) + 4) * (wide[j] ? 2 : 1), tmp.n);
     dev::GroupReduceColumn((const int32_t *)slot_of->p, data, phys, c.validity, tmp.n,
                            (dev::AggState *)states[j]->p, e.stream);
+    // MIN / MAX of a 128-bit value: a second pass over the column for the low words
+    if (wide[j])
+      dev::GroupMinMax128((const int32_t *)slot_of->p, data, phys, c.validity, tmp.n, (dev::AggState *)states[j]->p,
+                          e.stream);
   }
   auto list = Alloc(e, nslots * 4);
   dev::CompactSlots((const unsigned long long *)cs->p, nslots, (int32_t *)list->p, e.d_scratch, e.stream);
@@ -1415,7 +1433,7 @@ static bool SlotGroupAggregate(Engine &e, const DRel &tmp, const BoundSelect &s,
                   (const int32_t *)list->p, e.d_scratch, ngroups,
                   [&](int j) {
                     return EmitIn{states[j] ? (dev::AggState *)states[j]->p : nullptr,
-                                  arg_idx[j] >= 0 ? ClassOf(tmp.cols[arg_idx[j]].type) : VC_I64};
+                                  arg_idx[j] >= 0 ? ClassOf(tmp.cols[arg_idx[j]].type) : VC_I64, wide[j] != 0};
                   },
                   D);
   out.n = ngroups;

@@ -234,6 +234,10 @@ void GroupAssign(const void *kcol, int kphys, const uint64_t *kvalid, int64_t km
                  int32_t *slot_of_row, unsigned long long *count_star, hipStream_t s);
 void GroupReduceColumn(const int32_t *slot_of_row, const void *col, int phys, const uint64_t *valid, int64_t n,
                        AggState *states, hipStream_t s);
+// After GroupReduceColumn over a 128-bit column (P_I128, P_U64), which leaves every slot's least / greatest
+// high word in min_i / max_i: the low words of each slot's MIN / MAX into min_f / max_f (as ReduceMinMax128)
+void GroupMinMax128(const int32_t *slot_of_row, const void *col, int phys, const uint64_t *valid, int64_t n,
+                    AggState *states, hipStream_t s);
 void InitAggStates(AggState *st, int64_t n, hipStream_t s);
 // st[0 .. n) empty, cs[0 .. nc) = count (a row count the host already knows)
 void InitAggStatesCounts(AggState *st, int64_t n, unsigned long long *cs, int64_t nc, hipStream_t s,

@@ -2625,10 +2625,11 @@ __global__ void group_reduce_kernel(const int32_t *slot_of_row, const void *col,
       unsigned long long old = atomicAdd(&st->sum_lo, (unsigned long long)lo);
       unsigned long long carry = (old + (unsigned long long)lo) < old ? 1ull : 0ull;
       atomicAdd((unsigned long long *)&st->sum_hi, (unsigned long long)hi + carry);
-      if (phys != P_I128) {
-        atomicMin(&st->min_i, (long long)lo);
-        atomicMax(&st->max_i, (long long)lo);
-      }
+      // a 128-bit value (UBIGINT: 64 unsigned bits under a zero high word) orders by its
+      // HIGH word first: the first half of its MIN / MAX (group_minmax128_kernel)
+      const long long m = phys == P_I128 || phys == P_U64 ? hi : lo;
+      atomicMin(&st->min_i, m);
+      atomicMax(&st->max_i, m);
     }
   }
 }
@@ -2638,6 +2639,30 @@ void GroupReduceColumn(const int32_t *slot_of_row, const void *col, int phys, co
   if (n <= 0) return;
   hipLaunchKernelGGL(group_reduce_kernel, dim3(GridFor(n, 256 * 8, NumCUs() * 8)), dim3(256), 0, s, slot_of_row, col,
                      phys, valid, n, states);
+  CHECK_LAUNCH();
+}
+
+// MIN / MAX of a 128-bit column per slot, the second half (reduce_minmax128_kernel
+// with a slot per row): group_reduce_kernel has left every slot's least and
+// greatest high word in min_i / max_i; the unsigned low words of the rows that
+// have their slot's high word fold into min_f / max_f.
+__global__ void group_minmax128_kernel(const int32_t *slot_of_row, const void *col, int phys, const uint64_t *valid,
+                                       int64_t n, AggState *states) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    if (!bit_valid(valid, i)) continue;
+    AggState *st = &states[slot_of_row[i]];
+    int64_t lo, hi;
+    load_phys(col, phys, i, lo, hi);
+    if (hi == st->min_i) atomicMin(&st->min_f, (unsigned long long)lo);
+    if (hi == st->max_i) atomicMax(&st->max_f, (unsigned long long)lo);
+  }
+}
+
+void GroupMinMax128(const int32_t *slot_of_row, const void *col, int phys, const uint64_t *valid, int64_t n,
+                    AggState *states, hipStream_t s) {
+  if (n <= 0) return;
+  hipLaunchKernelGGL(group_minmax128_kernel, dim3(GridFor(n, 256 * 8, NumCUs() * 8)), dim3(256), 0, s, slot_of_row,
+                     col, phys, valid, n, states);
   CHECK_LAUNCH();
 }
 

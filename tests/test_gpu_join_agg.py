@@ -369,7 +369,8 @@ def test_decimal_double_date_and_negative_values(cc):
         got = row(c, "SELECT SUM(tt.x), AVG(tt.x), MIN(tt.x), MAX(tt.x), SUM(tt.x * td.w) FROM tt JOIN td ON tt.k = td.k")
         assert abs(float(got[0]) - sum(xs)) <= tol
         assert abs(float(got[1]) - sum(xs) / len(xs)) <= tol / len(xs)
-        assert abs(float(got[2]) - min(xs)) <= 1e-9 * abs(min(xs)) and abs(float(got[3]) - max(xs)) <= 1e-9 * abs(max(xs))
+        # MIN / MAX pick one of the values: exact (DOUBLE text is shortest round-trip)
+        assert float(got[2]) == min(xs) and float(got[3]) == max(xs), got
         assert abs(float(got[4]) - sum(dbl[i] * (i % 20) for i in hit)) <= 20 * tol
     assert took_fused(cc.fused)
     # a double sum is the same every time: the partials merge in a fixed order

@@ -128,8 +128,10 @@ def test_sharded_rows_and_hash_groups_vs_numpy(mbx, oracle, force_peer):
     assert abs(float(got[0]) - avg) <= 1e-12 * abs(avg)
     # DOUBLE sums: summation order differs between shards (stated tolerance 1e-9 relative)
     got = [float(v) for v in rows("SELECT SUM(f), AVG(f), MIN(f), MAX(f) FROM h")[0]]
-    for u, w in zip(got, [float(fv.sum()), float(fv.mean()), float(fv.min()), float(fv.max())]):
+    for u, w in zip(got[:2], [float(fv.sum()), float(fv.mean())]):
         assert abs(u - w) <= 1e-9 * abs(w)
+    # ... while MIN / MAX pick one of the values: exact (DOUBLE text is shortest round-trip)
+    assert got[2:] == [float(fv.min()), float(fv.max())], got
     # stream read-back of a sharded SELECT: the rows in part (= row) order
     st = c.query_stream("SELECT r FROM h WHERE x > 40").value
     got = []
