@@ -90,6 +90,7 @@ _sig("duckdb_mbx_statement_plan_stats", _I, _P, ctypes.POINTER(ctypes.c_int64))
 _sig("duckdb_mbx_shard_stats", _I, _P, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_double))
 _sig("duckdb_mbx_engine_stats", _I, _P, ctypes.POINTER(ctypes.c_int64))
 _sig("duckdb_mbx_result_tail_stats", _I, _P, ctypes.POINTER(ctypes.c_int64))
+_sig("duckdb_mbx_tail_wait_stats", _I, _P, ctypes.POINTER(ctypes.c_int64))
 _sig("duckdb_mbx_shard_timings", _I, _P, ctypes.POINTER(ctypes.c_double), _I)
 _sig("duckdb_mbx_shard_partial", _P, _P, _I)
 _sig("duckdb_mbx_rccl_stats", _I, _P, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_double))
@@ -638,6 +639,15 @@ class Connection:
         out = (ctypes.c_int64 * 2)()
         lib.duckdb_mbx_result_tail_stats(self._h, out)
         return {"tail": out[0], "host_copy": out[1]}
+
+    def tail_wait_stats(self) -> dict:
+        """How the host waited for the result tails (extension): statements
+        whose row it read on its ticket by polling (mbx_tail_spin_us), statements
+        that blocked on the stream, the nanoseconds spent waiting, and the
+        profile event pairs the engine holds."""
+        out = (ctypes.c_int64 * 4)()
+        lib.duckdb_mbx_tail_wait_stats(self._h, out)
+        return {"polled": out[0], "blocked": out[1], "wait_ns": out[2], "event_pairs": out[3]}
 
     def shard_timings(self) -> list:
         """The last sharded dispatch, per shard (extension): device and the us

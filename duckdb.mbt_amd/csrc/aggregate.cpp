@@ -128,6 +128,10 @@ static DRel EmitOneRow(Engine &e, const BoundSelect &s, const unsigned long long
     }
     D.host.err_src = e.d_err;
     D.host.err_dst = (int32_t *)e.h_mapped;
+    // a fresh ticket for this row (never 0, never reused): ToHost waits for it
+    D.host.ticket_dst = (uint64_t *)(e.h_mapped + kTailTicketOffset);
+    D.host.ticket = ++e.tail_ticket;
+    mark->ticket = D.host.ticket;
     out.tail = mark;
   }
   if (launch) launch(D);

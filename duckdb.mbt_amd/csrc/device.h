@@ -416,13 +416,18 @@ struct EmitDesc {
   // workgroup: with err_dst set, the lane that stores aggregate j's cell also
   // stores it to out[j] and the row's 64-bit validity word to valid[j], both in
   // the engine's coherent mapped buffer, then copies the device error word and
-  // fences at system scope, so the host reads the result after the stream wait
-  // with no copy kernel in between
+  // fences at system scope, with no copy kernel in between.  Last of all the
+  // same thread stores the statement's ticket (never 0, never reused) to
+  // ticket_dst with release at system scope: a host that reads that value
+  // there with acquire may read the error word and the row at once, without
+  // waiting for the stream (tail_wait.h)
   struct {
     void *out[EMIT_MAX_AGGS];
     uint64_t *valid[EMIT_MAX_AGGS];
     const int32_t *err_src;
     int32_t *err_dst;
+    uint64_t *ticket_dst;
+    uint64_t ticket;
   } host;
 };
 void EmitAggRelation(const EmitDesc &d, hipStream_t s);

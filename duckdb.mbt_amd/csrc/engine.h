@@ -211,6 +211,13 @@ struct Options {
   // is the statement's result (result_tail.h), so no copy kernel follows
   // (false: every small result is copied by one)
   bool result_tail = true;
+  // "mbx_tail_spin_us": how long a statement that took the result tail spins on
+  // its ticket before it blocks on the stream (tail_wait.h); 0: never spin.
+  // The default clears the slowest histogram step measured by an order of
+  // magnitude and stays well under the 0.29 ms of a full scan that ends in the
+  // same tail, which therefore blocks after 100 us and burns no core
+  // (profiles/tail_wait/README.md)
+  int64_t tail_spin_us = 100;
   // "mbx_join_max_rows": a join whose matches number more than this fails
   // with an Out of Range error before its result is allocated (one accidental
   // near-cross-product must not ask a shared card's pool for hundreds of GB)
@@ -385,5 +392,11 @@ void EngineCounters(const Connection &c, int64_t out[3]);
 // out[0] += small results read from the emit's host tail, out[1] += small
 // results copied by the copy kernel, over the connection and its shards
 void ResultTailCounters(const Connection &c, int64_t out[2]);
+// {statements whose result tail the host polled, statements that blocked on
+// the stream for it, ns spent in that wait, profile event pairs made}
+void TailWaitCounters(const Connection &c, int64_t out[4]);
+// reads the kernel times of statements whose profile is still pending into
+// last_profile and profile_history (before either is looked at)
+void SettleConnProfile(Connection &c);
 
 }  // namespace mbx

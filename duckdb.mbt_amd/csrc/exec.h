@@ -16,6 +16,7 @@
 #include "device.h"
 #include "engine.h"
 #include "result_tail.h"
+#include "tail_wait.h"
 
 namespace mbx {
 #define HIPCHK(x)                                                                            \
@@ -143,6 +144,17 @@ struct Engine {
   bool result_tail = true;
   uint64_t tail_serial = 0;
   int64_t tail_results = 0, hostcopy_results = 0;
+  // The result tail's ticket (tail_wait.h): EmitOneRow advances it each time it
+  // takes the tail and hands the new value to the emit, which stores it at
+  // h_mapped + kTailTicketOffset after the row; ToHost waits for exactly that
+  // value, spinning for up to tail_spin_ns (mbx_tail_spin_us, set by Eng; 0:
+  // block on the stream at once).  stream_draining: the last statement
+  // returned on its ticket, so its kernel's last instructions and the
+  // profile's closing event may still be on the stream.
+  uint64_t tail_ticket = 0;
+  int64_t tail_spin_ns = 0;
+  bool stream_draining = false;
+  TailWaitStats tail_wait;  // duckdb_mbx_tail_wait_stats
   // H2D ingest ring: host rows are copied into a pinned slot while the DMA of
   // the previous slot runs (bulk appender path)
   static constexpr int kStageSlots = 4;
@@ -180,19 +192,34 @@ struct Engine {
   std::mutex shard_mu;
   std::vector<QueryProfile::Kernel> shard_kernels;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool;  // reused across queries
-  size_t ev_used = 0;
-  // The per-kernel profile's event pairs: timing only (FinishProfile reads them
-  // after a stream synchronisation), so without the system-scope fence a
+  // which pairs of ev_pool are out: with the running statement, or with
+  // statements whose profile is not settled yet (pending_prof, oldest first;
+  // SettleProfile reads them and gives their pairs back)
+  EventPairLedger ev_ledger;
+  struct PendingProfile {
+    std::vector<ProfEvent> events;
+    std::vector<QueryProfile::Kernel> shard_kernels;
+  };
+  std::vector<PendingProfile> pending_prof;
+  // The per-kernel profile's event pairs: timing only (SettleProfile reads them
+  // after waiting for the last one), so without the system-scope fence a
   // recorded event otherwise performs (an L2 writeback and invalidate around
-  // each timestamp, which also delays the next launch on the stream)
+  // each timestamp, which also delays the next launch on the stream).  A pair
+  // that a pending statement holds is not handed out.
   std::pair<hipEvent_t, hipEvent_t> NextEvents() {
-    if (ev_used == ev_pool.size()) {
+    const size_t i = ev_ledger.Take();
+    if (i == ev_pool.size()) {
       hipEvent_t a, b;
       (void)hipEventCreateWithFlags(&a, hipEventDisableSystemFence);
       (void)hipEventCreateWithFlags(&b, hipEventDisableSystemFence);
       ev_pool.push_back({a, b});
     }
-    return ev_pool[ev_used++];
+    return ev_pool[i];
+  }
+  // a statement begins (or ends unread): the running statement's events go
+  void ResetEvents() {
+    events.clear();
+    ev_ledger.DropCurrent();
   }
   ~Engine() {
     if (has_gpu) {
@@ -288,6 +315,7 @@ struct DCol {
 // statement that made it.
 struct ResultTailMark {
   uint64_t serial = 0;  // Engine::tail_serial when it was made
+  uint64_t ticket = 0;  // what the emit stores behind the row (Engine::tail_ticket)
   size_t ncols = 0;
   const void *data[EMIT_MAX_AGGS];
   const void *valid[EMIT_MAX_AGGS];
@@ -341,7 +369,17 @@ size_t VisibleCols(const BoundSelect &s);
 DRel RunSelectDev(Engine &e, Connection &c, const BoundSelect &s, bool top = false);
 bool IsHostConstantSelect(const BoundSelect &s);
 ResultPtr HostConstantSelect(const BoundSelect &s);
+// The statement's profile: total_ms now; its kernels' times at once, or, where
+// the statement returned on its ticket with the stream still draining
+// (Engine::stream_draining), when SettleProfile next runs.
 void FinishProfile(Connection &c, Engine &e, double total_ms);
+// Reads the event pairs of every statement FinishProfile left pending into
+// last_profile and profile_history, in statement order (waits for the last
+// event).  At the start of every statement that resets the engine's events,
+// before the profile getters answer, and before the engine goes away.
+void SettleProfile(Connection &c, Engine &e);
+// a statement begins: SettleProfile, then e.profile from the connection and no events
+void BeginProfile(Connection &c, Engine &e);
 // ---- aggregate.cpp
 DRel Aggregate(Engine &e, const DRel &src, const BoundSelect &s);
 // the one-row relation of s's aggregates (no GROUP BY) from states[j] and the COUNT(*) word

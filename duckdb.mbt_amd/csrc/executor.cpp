@@ -76,6 +76,7 @@ std::shared_ptr<Engine> CreateEngine(int device, bool allow_no_gpu) {
   e->h_pinned_bytes = 1 << 20;
   HIPCHK(hipHostMalloc((void **)&e->h_pinned, e->h_pinned_bytes, hipHostMallocDefault));
   HIPCHK(hipHostMalloc((void **)&e->h_mapped, Engine::kMappedBytes, hipHostMallocCoherent | hipHostMallocMapped));
+  memset(e->h_mapped, 0, Engine::kMappedBytes);  // the ticket word reads 0, which no statement's ticket is
   e->has_gpu = true;
   return e;
 }
@@ -130,6 +131,7 @@ Engine &Eng(Connection &c) {
   e.scan_hist = c.opts.scan_hist;
   e.scan_hist_min_rows = c.opts.scan_hist_min_rows;
   e.result_tail = c.opts.result_tail;
+  e.tail_spin_ns = c.opts.tail_spin_us * 1000;
   SettlePending(e);  // a statement never sees a column before its appended stats
   return e;
 }
@@ -1466,7 +1468,23 @@ static ResultPtr ToHostPinned(Engine &e, const DRel &r, const std::vector<std::s
     dev::HostCopy(hd, e.stream);
     e.hostcopy_results++;
   }
-  HIPCHK(hipStreamSynchronize(e.stream));
+  if (tail) {
+    // the row's ticket, not the stream: the emit stored it last, with release
+    // (tail_wait.h); the error word and the cells are read only after it
+    const uint64_t *tk = (const uint64_t *)(H + kTailTicketOffset);
+    const TailWaitOutcome w = TailWait(
+        r.tail->ticket, e.tail_spin_ns, [&] { return __atomic_load_n(tk, __ATOMIC_ACQUIRE); },
+        [] {
+          return (int64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(
+                     std::chrono::steady_clock::now().time_since_epoch())
+              .count();
+        },
+        [&] { HIPCHK(hipStreamSynchronize(e.stream)); }, e.tail_wait);
+    if (w == TailWaitOutcome::kLost) ThrowError("Internal", "the result tail's ticket did not arrive with the stream");
+    e.stream_draining = w == TailWaitOutcome::kPolled;
+  } else {
+    HIPCHK(hipStreamSynchronize(e.stream));
+  }
   int32_t err;
   memcpy(&err, (const void *)H, 4);
   RaiseDeviceError(e, err);
@@ -1786,45 +1804,79 @@ ResultPtr HostConstantSelect(const BoundSelect &s) {
 }
 
 void FinishProfile(Connection &c, Engine &e, double total_ms) {
-  QueryProfile &p = c.last_profile;
-  p.kernels.clear();
-  p.total_ms = total_ms;
+  const bool draining = e.stream_draining;
+  e.stream_draining = false;
   if (!e.profile) {
+    QueryProfile &p = c.last_profile;
+    p.kernels.clear();
+    p.total_ms = total_ms;
     e.shard_kernels.clear();
     return;
   }
-  hipStreamSynchronize(e.stream);
-  for (auto &ev : e.events) {
-    float ms = 0;
-    hipEventElapsedTime(&ms, ev.a, ev.b);
-    QueryProfile::Kernel k;
-    k.name = ev.name;
-    k.ms = ms;
-    k.bytes = ev.bytes;
-    k.rows = ev.rows;
-    p.kernels.push_back(k);
-    if (c.profile_history.size() < 100000) c.profile_history.push_back(k);
+  // the statement's events and its shards' times wait with the engine, their
+  // event pairs out of circulation, until SettleProfile reads them
+  SettleProfile(c, e);  // (nothing is pending where the statement began with BeginProfile; else keep the order)
+  Engine::PendingProfile pp;
+  pp.events.swap(e.events);
+  pp.shard_kernels.swap(e.shard_kernels);
+  e.pending_prof.push_back(std::move(pp));
+  e.ev_ledger.Defer();
+  c.last_profile.kernels.clear();
+  c.last_profile.total_ms = total_ms;
+  // a statement that ended in a stream wait reads its times at once, as ever;
+  // one that returned on its ticket leaves the closing event to run out behind it
+  if (!draining) SettleProfile(c, e);
+}
+
+void SettleProfile(Connection &c, Engine &e) {
+  if (e.pending_prof.empty()) return;
+  QueryProfile &p = c.last_profile;
+  for (size_t i = e.pending_prof.size(); i-- > 0;)  // the last event recorded: every other one is before it on the stream
+    if (!e.pending_prof[i].events.empty()) {
+      hipEventSynchronize(e.pending_prof[i].events.back().b);
+      break;
+    }
+  for (auto &pp : e.pending_prof) {
+    p.kernels.clear();
+    for (auto &ev : pp.events) {
+      float ms = 0;
+      hipEventElapsedTime(&ms, ev.a, ev.b);
+      QueryProfile::Kernel k;
+      k.name = ev.name;
+      k.ms = ms;
+      k.bytes = ev.bytes;
+      k.rows = ev.rows;
+      p.kernels.push_back(k);
+      if (c.profile_history.size() < 100000) c.profile_history.push_back(k);
+    }
+    for (auto &k : pp.shard_kernels) {
+      p.kernels.push_back(k);
+      if (c.profile_history.size() < 100000) c.profile_history.push_back(k);
+    }
   }
-  for (auto &k : e.shard_kernels) {
-    p.kernels.push_back(k);
-    if (c.profile_history.size() < 100000) c.profile_history.push_back(k);
-  }
-  e.shard_kernels.clear();
-  e.events.clear();
-  e.ev_used = 0;
+  e.pending_prof.clear();
+  e.ev_ledger.Settle([](uint64_t, size_t) {});
+}
+
+// A statement begins: what earlier ones left pending is read first (their
+// event pairs come back), then the engine's events start empty.
+void BeginProfile(Connection &c, Engine &e) {
+  SettleProfile(c, e);
+  e.profile = c.opts.profile;
+  e.stream_draining = false;
+  e.ResetEvents();
 }
 
 ResultPtr ExecuteSelect(Connection &c, const BoundSelect &s) {
   auto t0 = std::chrono::steady_clock::now();
   if (IsHostConstantSelect(s)) {
     ResultPtr r = HostConstantSelect(s);
+    SettleConnProfile(c);  // (an earlier statement's pending times belong in front of this empty profile)
     c.last_profile = QueryProfile();
     return r;
   }
   Engine &e = Eng(c);
-  e.profile = c.opts.profile;
-  e.events.clear();
-  e.ev_used = 0;
+  BeginProfile(c, e);
   e.tail_serial++;  // no ResultTailMark of an earlier statement matches from here on
   if (c.sharded()) {
     if (ResultPtr hr = ShardedAggregateHost(c, s)) {
@@ -1857,9 +1909,7 @@ DeviceResultPtr ExecuteSelectDevice(Connection &c, const BoundSelect &s, StreamS
   if (IsHostConstantSelect(s)) return nullptr;
   auto t0 = std::chrono::steady_clock::now();
   Engine &e = Eng(c);
-  e.profile = c.opts.profile;
-  e.events.clear();
-  e.ev_used = 0;
+  BeginProfile(c, e);
   e.tail_serial++;
   auto d = std::make_shared<DeviceResult>();
   d->r = RunSelectDev(e, c, s, true);
@@ -1965,6 +2015,7 @@ bool CopyDeviceColumnText(Connection &c, DeviceResult &d, int col, const std::fu
   CheckError(e);
   if (out_bytes) LinkCopy(e, host, buf->p, out_bytes);
   if (e.profile) {  // a getter runs after its query's profile was taken: its kernels go to the drain history
+    SettleProfile(c, e);  // (behind those of every statement before it)
     for (auto &ev : e.events) {
       float ms = 0;
       hipEventElapsedTime(&ms, ev.a, ev.b);
@@ -1975,8 +2026,7 @@ bool CopyDeviceColumnText(Connection &c, DeviceResult &d, int col, const std::fu
       k.rows = ev.rows;
       if (c.profile_history.size() < 100000) c.profile_history.push_back(k);
     }
-    e.events.clear();
-    e.ev_used = 0;
+    e.ResetEvents();
   }
   return true;
 }
@@ -1988,6 +2038,23 @@ void EngineCounters(const Connection &c, int64_t out[3]) {
     out[2] += c.engine->sr_launch_failures;
   }
   for (auto &sc : c.shards) EngineCounters(*sc, out);
+}
+
+void TailWaitCounters(const Connection &c, int64_t out[4]) {
+  if (c.engine) {
+    out[0] += c.engine->tail_wait.polled;
+    out[1] += c.engine->tail_wait.blocked;
+    out[2] += c.engine->tail_wait.wait_ns;
+    out[3] += (int64_t)c.engine->ev_pool.size();
+  }
+  for (auto &sc : c.shards) TailWaitCounters(*sc, out);
+}
+
+void SettleConnProfile(Connection &c) {
+  if (c.engine && c.engine->has_gpu && !c.engine->pending_prof.empty()) {
+    hipSetDevice(c.engine->device);
+    SettleProfile(c, *c.engine);
+  }
 }
 
 void ResultTailCounters(const Connection &c, int64_t out[2]) {

@@ -344,9 +344,7 @@ void ExecuteInsertSelect(Connection &c, Table &t, const BoundSelect &s, const st
   if (t.sharded()) return ShardedInsertSelect(c, t, s, col_map);
   auto t0 = std::chrono::steady_clock::now();
   Engine &e = Eng(c);
-  e.profile = c.opts.profile;  // the statement's kernels (query, append copy, zone map) become last_profile
-  e.events.clear();
-  e.ev_used = 0;
+  BeginProfile(c, e);  // the statement's kernels (query, append copy, zone map) become last_profile
   DRel r;
   if (IsHostConstantSelect(s)) {
     ResultPtr hr = HostConstantSelect(s);

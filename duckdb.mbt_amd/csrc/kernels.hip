@@ -2781,6 +2781,10 @@ __device__ __forceinline__ void emit_one_row(const EmitDesc &D, const Acc &T0, i
   if (host) {
     *D.host.err_dst = err;
     __threadfence_system();
+    // the ticket, last: this thread alone wrote the cells, the validity words
+    // and the error word above (its callers run it on thread 0 of the one
+    // workgroup that emits), so a host that sees the ticket sees them all
+    __hip_atomic_store(D.host.ticket_dst, D.host.ticket, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
   }
 }
 
@@ -2865,9 +2869,14 @@ __device__ __forceinline__ void emit_agg_body(const EmitDesc &D, Acc *part, int6
   if (D.host.err_dst) {
     // the host tail: the cells and validity words above went to the mapped
     // buffer too; the error word follows them (one workgroup, one row: thread 0
-    // stored every one), visible to the host once the stream has drained
+    // stored every one), then the ticket, by the same thread: the launch is one
+    // workgroup (EmitAggRelation refuses any other shape with a host tail), row
+    // 0 is thread 0's, and so is word 0 of every bitmap, so thread 0 is the
+    // tail's only writer and its release orders all of it before the ticket
     if (bid == 0 && threadIdx.x == 0) *D.host.err_dst = *D.host.err_src;
     __threadfence_system();
+    if (bid == 0 && threadIdx.x == 0)
+      __hip_atomic_store(D.host.ticket_dst, D.host.ticket, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
   }
 }
 
@@ -3293,6 +3302,8 @@ namespace dev {
 void EmitAggRelation(const EmitDesc &d, hipStream_t s) {
   if (d.host.err_dst && (d.nslots != 1 || d.slot_list))
     throw std::runtime_error("EmitAggRelation: the host tail takes exactly one row");
+  if (d.host.err_dst && (!d.host.ticket_dst || !d.host.ticket))
+    throw std::runtime_error("EmitAggRelation: a host tail without a ticket");
   hipLaunchKernelGGL(emit_agg_kernel, dim3(d.npartials > 0 ? 1 : GridFor(d.nslots, 256, 1024)), dim3(256), 0, s, d);
   CHECK_LAUNCH();
 }

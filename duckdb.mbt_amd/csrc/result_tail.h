@@ -16,12 +16,23 @@
 // ResultTailDecide says which statements take it; ResultFitsMapped is the
 // copy decision ToHost makes, shared so the two cannot drift apart.
 //
+//
+// The first 64-byte line holds the error word at [0, 4) and, at
+// [kTailTicketOffset, kTailTicketOffset + 8), the ticket of the result tail:
+// the 64-bit count of the statement whose row the buffer holds, stored last by
+// the emitting thread with release at system scope (EmitDesc::host.ticket_dst,
+// tail_wait.h).  Nothing else writes that word: host_copy_kernel leaves it
+// alone, and the buffer is zeroed when it is allocated, so it reads 0 until
+// the first tail.  ResultBufferLayout never places a column below byte 64.
+//
 // Plain C++, no HIP: the executor includes it, and so does a host test.
 #pragma once
 #include <cstddef>
 #include <cstdint>
 
 namespace mbx {
+
+constexpr size_t kTailTicketOffset = 8;
 
 constexpr size_t ResultPad(size_t bytes) { return (bytes + 63) & ~(size_t)63; }
 

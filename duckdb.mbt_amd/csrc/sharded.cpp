@@ -148,9 +148,10 @@ static void ForShards(Connection &c, const std::function<void(int)> &f) {
 
 static Engine &ShardEngine(Connection &top, Connection &sc) {
   Engine &se = Eng(sc);
+  // (a shard engine takes no result tail, so none of its statements leaves a
+  // profile pending: ShardCollect reads its events after a stream wait)
   se.profile = top.opts.profile;
-  se.events.clear();
-  se.ev_used = 0;
+  se.ResetEvents();
   return se;
 }
 
@@ -176,8 +177,7 @@ static void ShardCollect(Engine &top, Engine &se, int shard, bool checked = fals
     k.device = se.device;
     ks.push_back(k);
   }
-  se.events.clear();
-  se.ev_used = 0;
+  se.ResetEvents();
   std::lock_guard<std::mutex> g(top.shard_mu);
   top.shard_kernels.insert(top.shard_kernels.end(), ks.begin(), ks.end());
 }

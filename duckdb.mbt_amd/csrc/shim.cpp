@@ -469,6 +469,9 @@ int32_t duckdb_mb_config_set(duckdb_mb_config *c, moonbit_bytes_t key, moonbit_b
   } else if (kl == "mbx_result_tail") {
     ok = v == "true" || v == "1" || v == "false" || v == "0";
     if (ok) c->opts.result_tail = v == "true" || v == "1";
+  } else if (kl == "mbx_tail_spin_us") {
+    ok = IsInt(v, &x) && x >= 0 && x <= 1000000;
+    if (ok) c->opts.tail_spin_us = x;
   } else if (kl == "mbx_join_max_rows") {
     ok = IsInt(v, &x) && x >= 0;
     if (ok) c->opts.join_max_rows = x;
@@ -1722,6 +1725,7 @@ int32_t duckdb_mbx_hbm_calibrate(duckdb_mb_connection *h, int64_t bytes, int32_t
 
 char *duckdb_mbx_last_profile(duckdb_mb_connection *h) {
   if (!h) return nullptr;
+  SettleConnProfile(h->conn);
   const QueryProfile &p = h->conn.last_profile;
   std::string j = "{\"total_ms\":" + std::to_string(p.total_ms) + ",\"kernels\":[";
   for (size_t i = 0; i < p.kernels.size(); i++) {
@@ -1737,6 +1741,7 @@ char *duckdb_mbx_last_profile(duckdb_mb_connection *h) {
 
 char *duckdb_mbx_profile_drain(duckdb_mb_connection *h) {
   if (!h) return nullptr;
+  SettleConnProfile(h->conn);
   std::string j = "[";
   for (size_t i = 0; i < h->conn.profile_history.size(); i++) {
     const auto &k = h->conn.profile_history[i];
@@ -1946,6 +1951,16 @@ int32_t duckdb_mbx_result_tail_stats(duckdb_mb_connection *h, int64_t *out2) {
   out2[0] = out2[1] = 0;
   ResultTailCounters(h->conn, out2);
   return 2;
+}
+
+// out4 = {statements whose result tail the host read on its ticket, statements
+// that blocked on the stream for it, nanoseconds spent in that wait, profile
+// event pairs the engines hold} over the connection and its shards.
+int32_t duckdb_mbx_tail_wait_stats(duckdb_mb_connection *h, int64_t *out4) {
+  if (!h || !out4) return 0;
+  out4[0] = out4[1] = out4[2] = out4[3] = 0;
+  TailWaitCounters(h->conn, out4);
+  return 4;
 }
 
 int32_t duckdb_mbx_result_raw(duckdb_mb_result *r, int32_t col, int32_t row, void *out, int32_t out_len) {

@@ -315,6 +315,14 @@ int32_t duckdb_mbx_engine_stats(duckdb_mb_connection *connection, int64_t *out3)
  * handle). */
 int32_t duckdb_mbx_result_tail_stats(duckdb_mb_connection *connection, int64_t *out2);
 
+/* How the host waited for the results of duckdb_mbx_result_tail_stats' first
+ * kind (mbx_tail_spin_us), over the connection and its shards: out4 =
+ * {statements whose row the host read on its ticket, by polling the mapped
+ * buffer; statements that blocked on the stream (all of them at
+ * mbx_tail_spin_us = 0); nanoseconds spent in that wait, both kinds; profile
+ * event pairs the engines hold}.  Returns 4 (0: no handle). */
+int32_t duckdb_mbx_tail_wait_stats(duckdb_mb_connection *connection, int64_t *out4);
+
 /* The last sharded dispatch, per shard i: out[4 i .. 4 i + 3] = {device,
  * wake_us, launch_us, done_us}, us since the dispatch began (the worker took
  * the job; its plan and launches were queued; its result reached the host:

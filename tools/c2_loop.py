@@ -5,9 +5,13 @@ GPU only.  Usage: c2_loop.py PROFILE(true|false) STEPS [SQL]
 
 C2_FLOORS0=1 sets the code, plane and histogram floors to 0, so the small table
 runs the kernels of the 1e9-row step (filter_agg_hist); C2_TAIL=false sets
-mbx_result_tail.  Run it under `rocprofv3 --kernel-trace` and give the output
+mbx_result_tail, C2_SPIN=US sets mbx_tail_spin_us (0: block on the stream).  The
+line it prints also carries duckdb_mbx_tail_wait_stats over the loop and the
+process's resident set in kB before and after it (the soak run of
+profiles/tail_wait/).  Run it under `rocprofv3 --kernel-trace` and give the output
 directory to tools/trace_gaps.py for the device timeline of a step
 (profiles/result_tail/)."""
+import array
 import json
 import os
 import statistics
@@ -28,15 +32,36 @@ if os.environ.get("C2_FLOORS0"):
         cfg.set(k, "0")
 if os.environ.get("C2_TAIL"):
     cfg.set("mbx_result_tail", os.environ["C2_TAIL"])
+if os.environ.get("C2_SPIN"):
+    cfg.set("mbx_tail_spin_us", os.environ["C2_SPIN"])
 c = m.connect_with_config(cfg).value
 c.query("CREATE TABLE t AS SELECT mbx_synth(42, i, 50) + 1 AS x FROM range(1000000) tbl(i)")
-ts = []
+
+
+def rss_kb():
+    with open("/proc/self/status") as f:
+        return next(int(ln.split()[1]) for ln in f if ln.startswith("VmRSS:"))
+
+
+for i in range(50):  # warm: the pool, the event pairs, the statement's allocations
+    c.query_raw(sql).close()
+if prof == "true":
+    c.profile_drain()
+ts = array.array("d", [0.0]) * steps  # (made before the first resident-set reading, so the loop allocates nothing)
+w0, rss0 = c.tail_wait_stats(), rss_kb()
 for i in range(steps):
     t0 = time.perf_counter()
     rr = c.query_raw(sql)
     v = rr.value(0, 0)
     rr.close()
-    ts.append(time.perf_counter() - t0)
+    ts[i] = time.perf_counter() - t0
+    if prof == "true" and (i + 1) % 50000 == 0:
+        c.profile_drain()  # (the history keeps 100000 entries)
+w1, rss1 = c.tail_wait_stats(), rss_kb()
+ts = sorted(ts)
 print(json.dumps({"profile": prof, "sql": sql, "steps": steps, "value": str(v),
-                  "median_us": statistics.median(ts[50:]) * 1e6, "min_us": min(ts) * 1e6}))
+                  "median_us": statistics.median(ts) * 1e6, "min_us": ts[0] * 1e6,
+                  "p90_us": ts[int(0.90 * (len(ts) - 1))] * 1e6, "p99_us": ts[int(0.99 * (len(ts) - 1))] * 1e6, "mean_us": sum(ts) / len(ts) * 1e6,
+                  "tail_wait": {k: w1[k] - w0[k] for k in ("polled", "blocked", "wait_ns")},
+                  "rss_kb": [rss0, rss1]}))
 c.close()
