@@ -799,6 +799,10 @@ struct BindCtx {
   bool in_agg_arg = false;
   // select-list aliases usable in GROUP BY / ORDER BY
   const std::vector<ExprPtr> *select_list = nullptr;
+  // where window calls may stand (the select list of a non-aggregate select):
+  // the select's calls; in_window: inside a call's arguments or keys
+  std::vector<WindowCall> *windows = nullptr;
+  bool in_window = false;
 };
 
 std::string ColumnName(const Expr &e);
@@ -816,6 +820,7 @@ std::string ColumnName(const Expr &e) {
     case Expr::CONST: return ConstText(e.val);
     case Expr::FUNC: {
       std::string n = Lower(e.name);
+      if (e.over && !e.text.empty()) return e.text;  // a window call is named by its text
       if (e.star && n == "count") return "count_star()";
       std::string s = n + "(" + (e.distinct ? "DISTINCT " : "");
       for (size_t i = 0; i < e.args.size(); i++) s += (i ? ", " : "") + ColumnName(*e.args[i]);
@@ -840,10 +845,25 @@ bool IsAggName(const std::string &n) {
          n == "count_star";
 }
 
+// (sum(x) OVER (..) is a window call, not an aggregate; an aggregate among its
+// arguments or keys is one)
 bool ContainsAgg(const Expr &e) {
-  if (e.kind == Expr::FUNC && IsAggName(Lower(e.name))) return true;
+  if (e.kind == Expr::FUNC && !e.over && IsAggName(Lower(e.name))) return true;
   for (auto &a : e.args)
     if (a && ContainsAgg(*a)) return true;
+  if (e.over) {
+    for (auto &p : e.over->partition)
+      if (ContainsAgg(*p)) return true;
+    for (auto &o : e.over->order)
+      if (ContainsAgg(*o.expr)) return true;
+  }
+  return false;
+}
+
+bool ContainsWindow(const Expr &e) {
+  if (e.over) return true;
+  for (auto &a : e.args)
+    if (a && ContainsWindow(*a)) return true;
   return false;
 }
 
@@ -956,10 +976,11 @@ BExprPtr BindStringMatch(BOp op, const char *what, BExprPtr s, BExprPtr pat, BEx
   return e;
 }
 
-BExprPtr BindAggregate(const Expr &e, BindCtx &ctx) {
+// The kind, the argument with its casts and the result type of the aggregate
+// call e; sub binds the argument.  The grouped aggregates and the window
+// aggregates type through here.
+AggSpec TypeAggregate(const Expr &e, BindCtx &sub) {
   std::string n = Lower(e.name);
-  if (!ctx.agg_mode || ctx.in_agg_arg)
-    ThrowError("Binder", "aggregate function calls cannot be nested or appear here: " + ColumnName(e));
   AggSpec a;
   a.distinct = e.distinct;
   if (e.star || n == "count_star") {
@@ -967,9 +988,6 @@ BExprPtr BindAggregate(const Expr &e, BindCtx &ctx) {
     a.type = LogicalType(T_BIGINT);
   } else {
     if (e.args.size() != 1) ThrowError("Binder", "No function matches the given name and argument types '" + n + "'");
-    BindCtx sub = ctx;
-    sub.agg_mode = false;
-    sub.in_agg_arg = true;
     BExprPtr arg = BindExpr(*e.args[0], sub);
     a.arg = arg;
     LogicalType at = arg->type;
@@ -998,6 +1016,16 @@ BExprPtr BindAggregate(const Expr &e, BindCtx &ctx) {
       a.type = at;
     }
   }
+  return a;
+}
+
+BExprPtr BindAggregate(const Expr &e, BindCtx &ctx) {
+  if (!ctx.agg_mode || ctx.in_agg_arg)
+    ThrowError("Binder", "aggregate function calls cannot be nested or appear here: " + ColumnName(e));
+  BindCtx sub = ctx;
+  sub.agg_mode = false;
+  sub.in_agg_arg = true;
+  AggSpec a = TypeAggregate(e, sub);
   if (a.distinct && a.kind != A_COUNT && a.kind != A_MIN && a.kind != A_MAX)
     ThrowError("Not implemented", "DISTINCT aggregates are not supported by the MI355X backend");
   if (a.distinct) a.distinct = a.kind == A_COUNT;  // MIN/MAX DISTINCT == MIN/MAX
@@ -1013,8 +1041,119 @@ BExprPtr BindAggregate(const Expr &e, BindCtx &ctx) {
   return MkCol(ng + (int)ctx.aggs->size() - 1, a.type);
 }
 
+static bool SameOrder(const std::vector<BoundOrder> &a, const std::vector<BoundOrder> &b) {
+  if (a.size() != b.size()) return false;
+  for (size_t i = 0; i < a.size(); i++)
+    if (a[i].desc != b[i].desc || a[i].nulls_first != b[i].nulls_first || !BoundEq(*a[i].expr, *b[i].expr)) return false;
+  return true;
+}
+static bool SameTrees(const std::vector<BExprPtr> &a, const std::vector<BExprPtr> &b) {
+  if (a.size() != b.size()) return false;
+  for (size_t i = 0; i < a.size(); i++)
+    if (!BoundEq(*a[i], *b[i])) return false;
+  return true;
+}
+
+// f(args) OVER (...): the call joins the select's window list (an identical
+// call binds once) and the expression reads its column, behind the source's.
+BExprPtr BindWindow(const Expr &e, BindCtx &ctx) {
+  const std::string n = Lower(e.name);
+  auto refuse = [](const std::string &what) {
+    ThrowError("Not implemented", what + " is not supported by the MI355X backend");
+  };
+  if (ctx.in_window) ThrowError("Binder", "window function calls cannot be nested");
+  if (!ctx.windows) ThrowError("Binder", "window functions are not allowed here: " + ColumnName(e));
+  const OverClause &ov = *e.over;
+  BindCtx sub = ctx;
+  sub.windows = nullptr;
+  sub.in_window = true;
+  sub.select_list = nullptr;
+  WindowCall w;
+  auto checked_arg = [&](BExprPtr a) {
+    if (a->type.id == T_SQLNULL) a = CastTo(a, LogicalType(T_INTEGER));
+    const Phys ph = PhysOf(a->type);
+    if (ph == P_STR || ph == P_INTERVAL)
+      refuse("a window function argument of type " + a->type.ToString() + " (" + n + ")");
+    return a;
+  };
+  if (n == "row_number" || n == "rank" || n == "dense_rank") {
+    if (!e.args.empty() || e.star)
+      ThrowError("Binder", "No function matches the given name and argument types '" + n + "(...)': " + n +
+                               "() takes no arguments");
+    w.kind = n == "row_number" ? W_ROW_NUMBER : n == "rank" ? W_RANK : W_DENSE_RANK;
+    w.type = LogicalType(T_BIGINT);
+  } else if (IsAggName(n)) {
+    if (e.distinct) refuse("DISTINCT inside a window aggregate");
+    AggSpec a = TypeAggregate(e, sub);
+    static const WinKind of[] = {W_COUNT_STAR, W_COUNT, W_SUM, W_MIN, W_MAX, W_AVG};
+    w.kind = of[a.kind];
+    w.type = a.type;
+    if (a.arg) w.arg = checked_arg(a.arg);
+  } else if (n == "lag" || n == "lead") {
+    if (e.args.empty() || e.star || e.distinct)
+      ThrowError("Binder", "No function matches the given name and argument types '" + n + "()'");
+    if (e.args.size() > 2) refuse(n + " with a third (default) argument");
+    w.kind = n == "lag" ? W_LAG : W_LEAD;
+    w.arg = checked_arg(BindExpr(*e.args[0], sub));
+    w.type = w.arg->type;
+    w.offset = 1;
+    if (e.args.size() == 2) {
+      BExprPtr k = BindExpr(*e.args[1], sub);
+      if (!IsConstTree(*k)) refuse(n + " with a non-constant offset");
+      Value v = EvalConst(*k);
+      if (v.is_null || !(IsIntegral(k->type.id))) refuse(n + " with an offset that is not an integer constant");
+      w.offset = (int64_t)CastValue(v, LogicalType(T_BIGINT)).i;
+      if (w.offset < 0) refuse(n + " with a negative offset");
+    }
+  } else if (n == "ntile" || n == "first_value" || n == "first" || n == "last_value" || n == "last" || n == "nth_value" ||
+             n == "percent_rank" || n == "cume_dist") {
+    std::string up = n;
+    for (auto &ch : up) ch = (char)toupper((unsigned char)ch);
+    refuse("the window function " + up);
+  } else {
+    ThrowError("Catalog", "Window function with name " + n + " does not exist!");
+  }
+  auto key = [&](const Expr &x) {
+    BExprPtr k = BindExpr(x, sub);
+    if (k->type.id == T_SQLNULL) k = CastTo(k, LogicalType(T_INTEGER));
+    const Phys ph = PhysOf(k->type);
+    if (ph == P_STR || ph == P_I128 || ph == P_INTERVAL)
+      refuse("a window PARTITION BY / ORDER BY key of type " + k->type.ToString());
+    return k;
+  };
+  for (auto &p : ov.partition) w.partition.push_back(key(*p));
+  for (auto &oi : ov.order) {
+    BoundOrder bo;
+    bo.desc = oi.desc;
+    bo.nulls_first = oi.nulls_first == 1;  // the default is NULLS LAST, as in the select's ORDER BY
+    bo.expr = key(*oi.expr);
+    w.order.push_back(bo);
+  }
+  w.frame = ov.unit == OverClause::NO_FRAME ? WFS_NONE
+            : ov.unit == OverClause::ROWS   ? (ov.to_unbounded_following ? WFS_ROWS_UNBOUNDED : WFS_ROWS_CURRENT)
+                                            : (ov.to_unbounded_following ? WFS_RANGE_UNBOUNDED : WFS_RANGE_CURRENT);
+  w.target = WinResolveFrame(w.kind, !w.order.empty(), w.frame);
+  const int nsrc = (int)ctx.scope.size();
+  std::vector<WindowCall> &all = *ctx.windows;
+  for (size_t i = 0; i < all.size(); i++) {
+    const WindowCall &o = all[i];
+    if (o.kind == w.kind && o.offset == w.offset && o.target == w.target && o.type == w.type &&
+        ((!o.arg && !w.arg) || (o.arg && w.arg && BoundEq(*o.arg, *w.arg))) && SameTrees(o.partition, w.partition) &&
+        SameOrder(o.order, w.order))
+      return MkCol(nsrc + (int)i, o.type);
+  }
+  all.push_back(w);
+  std::vector<int> spec(all.size());
+  WinGroupSpecs((int)all.size(), [&](int a, int b) {
+    return SameTrees(all[a].partition, all[b].partition) && SameOrder(all[a].order, all[b].order);
+  }, spec.data());
+  for (size_t i = 0; i < all.size(); i++) all[i].spec = spec[i];
+  return MkCol(nsrc + (int)all.size() - 1, w.type);
+}
+
 BExprPtr BindFunction(const Expr &e, BindCtx &ctx) {
   std::string n = Lower(e.name);
+  if (e.over) return BindWindow(e, ctx);
   if (IsAggName(n)) return BindAggregate(e, ctx);
   std::vector<BExprPtr> args;
   for (auto &a : e.args) args.push_back(BindExpr(*a, ctx));
@@ -1353,6 +1492,7 @@ static void BindJoinCondition(const TableRef &tr, BoundSource &src, const std::v
   LogicalType refused;  // the type of a two-sided equality that cannot be a key
   for (auto &cj : conj) {
     if (ContainsAgg(*cj)) ThrowError("Binder", "JOIN condition cannot contain aggregates!");
+    if (ContainsWindow(*cj)) ThrowError("Binder", "JOIN condition cannot contain window functions!");
     BExprPtr b = CastTo(BindExpr(*cj, ctx), LogicalType(T_BOOLEAN));
     if (!src.left_key && b->kind == BExpr::FUNC && b->op == B_EQ && b->ch.size() == 2) {
       const int s0 = JoinSides(*b->ch[0], nleft), s1 = JoinSides(*b->ch[1], nleft);
@@ -1506,6 +1646,7 @@ static BoundSelectPtr BindSelectOne(const Select &sel, Catalog &cat, const std::
 
   if (sel.where) {
     if (ContainsAgg(*sel.where)) ThrowError("Binder", "WHERE clause cannot contain aggregates!");
+    if (ContainsWindow(*sel.where)) ThrowError("Binder", "WHERE clause cannot contain window functions!");
     BindCtx ctx = base;
     ctx.select_list = nullptr;
     BExprPtr w = BindExpr(*sel.where, ctx);
@@ -1516,6 +1657,18 @@ static BoundSelectPtr BindSelectOne(const Select &sel, Catalog &cat, const std::
   for (auto &e : list)
     if (ContainsAgg(*e)) has_agg = true;
   bs->is_agg = has_agg || sel.distinct;
+  for (auto &g : sel.group_by)
+    if (ContainsWindow(*g)) ThrowError("Binder", "GROUP BY clause cannot contain window functions!");
+  if (sel.having && ContainsWindow(*sel.having)) ThrowError("Binder", "HAVING clause cannot contain window functions!");
+  bool has_window = false;
+  for (auto &e : list) has_window |= ContainsWindow(*e);
+  if (has_window && bs->is_agg)
+    ThrowError("Not implemented",
+               "a window function in a select that also aggregates (GROUP BY, HAVING, an aggregate in the list, SELECT "
+               "DISTINCT) is not supported by the MI355X backend (put the aggregate in a subquery and the window over it)");
+  if (has_window && bs->src.kind == BoundSource::TABLE && bs->src.table && bs->src.table->sharded())
+    ThrowError("Not implemented", "a window function over table \"" + bs->src.table->name +
+                                      "\", which is sharded by gpu_devices, is not supported by the MI355X backend");
 
   std::vector<std::string> names;
   for (auto &e : list) names.push_back(ColumnName(*e));
@@ -1546,7 +1699,9 @@ static BoundSelectPtr BindSelectOne(const Select &sel, Catalog &cat, const std::
     for (auto &e : list) bs->outputs.push_back(BindExpr(*e, actx));
     if (sel.having) bs->having = CastTo(BindExpr(*sel.having, actx), LogicalType(T_BOOLEAN));
   } else {
-    for (auto &e : list) bs->outputs.push_back(BindExpr(*e, base));
+    BindCtx octx = base;
+    octx.windows = &bs->windows;
+    for (auto &e : list) bs->outputs.push_back(BindExpr(*e, octx));
   }
   for (auto &o : bs->outputs)
     if (o->type.id == T_SQLNULL) {
@@ -1602,6 +1757,9 @@ BoundSelectPtr BindSelect(const Select &sel, Catalog &cat, const std::vector<Val
     }
     if (idx < 0) {
       if (!first->union_all.empty()) ThrowError("Binder", "ORDER BY of a UNION must refer to an output column");
+      if (ContainsWindow(e))
+        ThrowError("Not implemented", "a window function in ORDER BY that is not also an output column is not supported "
+                                      "by the MI355X backend (name it in the select list and order by its alias)");
       // hidden sort key: bind over the source (or the aggregate relation)
       BindCtx ctx;
       ctx.params = &params;
@@ -1627,6 +1785,7 @@ BoundSelectPtr BindSelect(const Select &sel, Catalog &cat, const std::vector<Val
 
 bool IsHostConstantSelect(const BoundSelect &s) {
   if (s.src.kind != BoundSource::ONE_ROW) return false;
+  if (!s.windows.empty()) return false;  // the window stage runs on the one-row source
   if (s.where && !IsConstTree(*s.where)) return false;
   for (auto &u : s.union_all)
     if (!IsHostConstantSelect(*u)) return false;
@@ -1676,6 +1835,25 @@ std::string ExplainSelect(const BoundSelect &s, int ind) {
              ") :: " + s.aggs[i].type.ToString();
     out += "]\n";
   }
+  for (auto &w : s.windows) {
+    static const char *wn[] = {"row_number", "rank", "dense_rank", "count_star", "count", "sum", "min", "max", "avg",
+                               "lag", "lead"};
+    out += pad + "  WINDOW " + wn[w.kind] + "(" + (w.arg ? ExprToString(*w.arg) : "");
+    if (w.kind == W_LAG || w.kind == W_LEAD) out += ", " + std::to_string(w.offset);
+    out += ")";
+    if (!w.partition.empty()) {
+      out += " PARTITION BY ";
+      for (size_t i = 0; i < w.partition.size(); i++) out += (i ? ", " : "") + ExprToString(*w.partition[i]);
+    }
+    if (!w.order.empty()) {
+      out += " ORDER BY ";
+      for (size_t i = 0; i < w.order.size(); i++)
+        out += (i ? ", " : "") + ExprToString(*w.order[i].expr) + (w.order[i].desc ? " DESC" : " ASC") +
+               (w.order[i].nulls_first ? " NULLS FIRST" : " NULLS LAST");
+    }
+    out += std::string(" FRAME ") + WinTargetName(w.target) + " SPEC " + std::to_string(w.spec) + " :: " +
+           w.type.ToString() + "\n";
+  }
   if (s.having) out += pad + "  HAVING " + ExprToString(*s.having) + "\n";
   for (auto &o : s.order) out += pad + "  ORDER BY " + ExprToString(*o.expr) + (o.desc ? " DESC" : " ASC") + "\n";
   if (s.limit >= 0) out += pad + "  LIMIT " + std::to_string(s.limit) + " OFFSET " + std::to_string(s.offset) + "\n";
@@ -1713,6 +1891,11 @@ static void CollectPlanNodes(const BoundSelect &s, std::set<const BExpr *> &out)
   CollectExprNodes(s.having.get(), out);
   for (auto &g : s.groups) CollectExprNodes(g.get(), out);
   for (auto &a : s.aggs) CollectExprNodes(a.arg.get(), out);
+  for (auto &w : s.windows) {
+    CollectExprNodes(w.arg.get(), out);
+    for (auto &p : w.partition) CollectExprNodes(p.get(), out);
+    for (auto &o : w.order) CollectExprNodes(o.expr.get(), out);
+  }
   for (auto &o : s.outputs) CollectExprNodes(o.get(), out);
   for (auto &o : s.order) CollectExprNodes(o.expr.get(), out);
   CollectSourceNodes(s.src, out);

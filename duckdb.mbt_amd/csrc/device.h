@@ -358,6 +358,71 @@ void JoinProbeAgg(const VmProgram &p, const VmCols &cols, const JoinAggArgs &a, 
 void JoinAggFold(const JoinAggRec *partials, const unsigned long long *block_counts, int blocks, int n_out,
                  AggState *states, unsigned long long *counts_out, hipStream_t s);
 
+// --- window functions (window_kernels.hip; window_plan.h) ---------------------
+// The PARTITION BY keys [0, npart) and then the ORDER BY keys of one
+// specification, as columns of the base relation.
+#define WIN_MAX_KEYS 16
+struct WinKeys {
+  int32_t nkeys, npart;
+  struct {
+    const void *data;
+    const uint64_t *valid;
+    int32_t phys;
+  } k[WIN_MAX_KEYS];
+};
+// flags[i] of sorted position i (row perm[i]; perm null: i): bit 0 a partition
+// starts here, bit 1 a peer group starts here.  Position 0 starts both.
+constexpr uint8_t kWinPartStart = 1, kWinPeerStart = 2;
+void WindowBounds(const WinKeys &K, const int64_t *perm, int64_t n, uint8_t *flags, hipStream_t s);
+
+enum WinScanOp : int32_t { WOP_POS, WOP_COUNT, WOP_SUM128, WOP_SUMF, WOP_MIN64, WOP_MAX64, WOP_MIN128, WOP_MAX128 };
+enum WinScanSrc : int32_t {
+  WSRC_POS,   // the position itself (WOP_POS): the first position of every segment
+  WSRC_PEER,  // 1 where a peer group starts (WOP_COUNT): DENSE_RANK
+  WSRC_COL,   // the argument column at perm[i], NULLs skipped
+};
+// One segmented inclusive scan over the n sorted positions.  backward: from
+// the last position to the first, a segment starting where the next position
+// (in memory) starts one; WOP_POS then gives every segment's last position.
+struct WinScanDesc {
+  int32_t op, src, backward;
+  int32_t seg_bit;  // the bit of flags that starts a segment
+  const uint8_t *flags;
+  const int64_t *perm;
+  const void *data;  // WSRC_COL
+  const uint64_t *valid;
+  int32_t phys;
+  int64_t n;
+  void *out;    // WOP_POS: int32 per position; else the op's state per position (WinStateBytes)
+  void *carry;  // WinTiles(n) x WinCarryBytes
+};
+size_t WinStateBytes(int op);
+size_t WinCarryBytes(int op);
+// the scan's three launches: every tile's carry; the carries scanned by one
+// workgroup; every tile finished with what it receives
+void WindowScanReduce(const WinScanDesc &D, hipStream_t s);
+void WindowScanCarry(const WinScanDesc &D, hipStream_t s);
+void WindowScanApply(const WinScanDesc &D, hipStream_t s);
+
+// One call's result column, written at perm[i] for every sorted position i.
+struct WinEmitDesc {
+  int32_t kind;    // WinKind
+  int32_t target;  // WinTarget: where the running state is read
+  int32_t op;      // the WinScanOp of `state`
+  int32_t in_phys, out_phys;
+  int32_t avg_scale;
+  int64_t offset;  // LAG / LEAD
+  int64_t n;
+  const int64_t *perm;
+  const int32_t *part_first, *part_last, *peer_first, *peer_last;  // those the call needs
+  const void *state;
+  const void *data;  // LAG / LEAD: the argument column
+  const uint64_t *valid;
+  void *out;
+  uint32_t *out_valid;  // zeroed bitmap; null for a result that is never NULL
+};
+void WindowEmit(const WinEmitDesc &D, hipStream_t s);
+
 int NumCUs();
 
 }  // namespace dev

@@ -1,7 +1,7 @@
 // exec.h — what the executor's translation units share (executor.cpp,
-// aggregate.cpp, join.cpp, ingest.cpp, sharded.cpp): the engine state, device buffers
+// aggregate.cpp, join.cpp, window.cpp, ingest.cpp, sharded.cpp): the engine state, device buffers
 // and relations, and the functions that cross between the units.  Internal to
-// those five files: the engine and the C-ABI shim see engine.h only.
+// those six files: the engine and the C-ABI shim see engine.h only.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -360,6 +360,7 @@ bool RangePredicate(const BExpr &p, int *col, i128 *lo, i128 *hi);
 bool RangeConj(const BExpr &p, std::map<int, std::pair<i128, i128>> &ranges);
 bool FastIntCol(const DRel &rel, int c);
 DRel GatherRel(Engine &e, const DRel &r, const int64_t *perm, int64_t n);
+DevBufPtr SortPerm(Engine &e, const DRel &r, const std::vector<BoundOrder> &order);
 DRel ConcatRels(Engine &e, std::vector<DRel> &parts);
 ResultPtr ToHost(Engine &e, const DRel &r, const std::vector<std::string> &names, int64_t offset, int64_t limit,
                  size_t ncols, bool text = false);
@@ -406,6 +407,9 @@ DRel JoinRel(Engine &e, Connection &c, const BoundSource &src);  // JoinPairs(Jo
 // probe-and-aggregate where join_agg_plan.h takes the statement, else from
 // JoinPairs on the same prepared join and Aggregate()
 DRel JoinAggregate(Engine &e, Connection &c, const BoundSelect &s);
+// ---- window.cpp
+// s: a select with window calls; src: its source relation.  The relation of s's outputs, in source order.
+DRel WindowBranch(Engine &e, const BoundSelect &s, const DRel &src);
 // ---- ingest.cpp
 void UpdateScanCodes(Engine &e, DevColumn &c, int64_t nrows);
 void AppendCast(Engine &e, Table &t, DRel r, const std::vector<int> &col_map);

@@ -1192,9 +1192,11 @@ DRel GatherRel(Engine &e, const DRel &r, const int64_t *perm, int64_t n) {
   return out;
 }
 
-static DRel SortRel(Engine &e, const DRel &r, const std::vector<BoundOrder> &order) {
+// The stable permutation that sorts r by `order` (whose expressions are
+// columns of r); null when there is nothing to sort: the identity.
+DevBufPtr SortPerm(Engine &e, const DRel &r, const std::vector<BoundOrder> &order) {
   int64_t n = r.n;
-  if (n <= 1 || order.empty()) return r;
+  if (n <= 1 || order.empty()) return nullptr;
   auto perm = Alloc(e, n * 8), perm2 = Alloc(e, n * 8);
   auto keys = Alloc(e, n * 8), keys2 = Alloc(e, n * 8);
   dev::Iota((int64_t *)perm->p, n, 0, e.stream);
@@ -1232,7 +1234,13 @@ static DRel SortRel(Engine &e, const DRel &r, const std::vector<BoundOrder> &ord
       pass(1);
     }
   }
-  DRel out = GatherRel(e, r, (const int64_t *)perm->p, n);
+  return perm;
+}
+
+static DRel SortRel(Engine &e, const DRel &r, const std::vector<BoundOrder> &order) {
+  DevBufPtr perm = SortPerm(e, r, order);
+  if (!perm) return r;
+  DRel out = GatherRel(e, r, (const int64_t *)perm->p, r.n);
   HIPCHK(hipStreamSynchronize(e.stream));
   return out;
 }
@@ -1658,6 +1666,7 @@ DRel RunBranch(Engine &e, Connection &c, const BoundSelect &s) {
     DRel agg = Aggregate(e, src, s);
     return FilterProject(e, agg, s.having, s.outputs);
   }
+  if (!s.windows.empty()) return WindowBranch(e, s, src);
   return FilterProject(e, src, s.where, s.outputs);
 }
 

@@ -8,6 +8,7 @@
 
 #include "sql.h"
 #include "types.h"
+#include "window_plan.h"
 
 namespace mbx {
 
@@ -70,12 +71,30 @@ struct BoundOrder {
   bool nulls_first = false;
 };
 
+// One window call f(arg) OVER (PARTITION BY .. ORDER BY .. frame).  Every tree
+// reads the source columns.  Calls of one select with equal partition and
+// order lists carry the same `spec` and share one sort (WinGroupSpecs).
+struct WindowCall {
+  WinKind kind = W_ROW_NUMBER;
+  BExprPtr arg;        // null for ROW_NUMBER / RANK / DENSE_RANK / COUNT(*)
+  int64_t offset = 0;  // LAG / LEAD
+  std::vector<BExprPtr> partition;
+  std::vector<BoundOrder> order;
+  WinFrameSpec frame = WFS_NONE;  // as written
+  WinTarget target = WT_SELF;     // resolved (WinResolveFrame)
+  int spec = 0;
+  LogicalType type;  // result type
+};
+
 struct BoundSelect {
   BoundSource src;
   BExprPtr where;  // over source columns
   bool is_agg = false;
   std::vector<BExprPtr> groups;  // over source columns
   std::vector<AggSpec> aggs;
+  // Window calls (never with is_agg); with any, the outputs read the relation
+  // [source columns..., window results...]
+  std::vector<WindowCall> windows;
   // Outputs.  Non-aggregate: over source columns.  Aggregate: over the
   // aggregate relation [groups..., aggs...].
   std::vector<BExprPtr> outputs;

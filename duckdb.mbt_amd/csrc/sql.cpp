@@ -386,26 +386,32 @@ class Parser {
       }
     }
     if (AcceptKw("having")) s->having = ParseExpr();
+    if (IsKw("qualify")) ThrowError("Not implemented", "QUALIFY is not supported by the MI355X backend");
+    if (IsKw("window"))
+      ThrowError("Not implemented", "named windows (WINDOW w AS ...) are not supported by the MI355X backend");
     return s;
+  }
+
+  OrderItem ParseOrderItem() {
+    OrderItem it;
+    it.expr = ParseExpr();
+    if (AcceptKw("desc")) it.desc = true;
+    else AcceptKw("asc");
+    if (AcceptKw("nulls")) {
+      if (AcceptKw("first")) it.nulls_first = 1;
+      else {
+        ExpectKw("last");
+        it.nulls_first = 0;
+      }
+    }
+    return it;
   }
 
   void ParseOrderLimit(Select *s) {
     if (AcceptKw("order")) {
       ExpectKw("by");
-      do {
-        OrderItem it;
-        it.expr = ParseExpr();
-        if (AcceptKw("desc")) it.desc = true;
-        else AcceptKw("asc");
-        if (AcceptKw("nulls")) {
-          if (AcceptKw("first")) it.nulls_first = 1;
-          else {
-            ExpectKw("last");
-            it.nulls_first = 0;
-          }
-        }
-        s->order_by.push_back(it);
-      } while (AcceptOp(","));
+      do s->order_by.push_back(ParseOrderItem());
+      while (AcceptOp(","));
     }
     for (int k = 0; k < 2; k++) {
       if (AcceptKw("limit")) s->limit = ParseExpr();
@@ -859,8 +865,14 @@ class Parser {
           while (AcceptOp(","));
         }
         ExpectOp(")");
-        if (IsKw("over") || IsKw("filter"))
-          ThrowError("Not implemented", "window functions / FILTER are not supported by the MI355X backend");
+        if (IsKw("filter") && Peek().k == Tok::OP && Peek().s == "(")
+          ThrowError("Not implemented", "FILTER (WHERE ...) on an aggregate is not supported by the MI355X backend");
+        if (IsKw("over")) {
+          p_++;
+          if (!IsOp("("))
+            ThrowError("Not implemented", "named windows (WINDOW w AS ...) are not supported by the MI355X backend");
+          f->over = ParseOver();
+        }
         return f;
       }
       auto c = Mk(Expr::COLREF);
@@ -879,6 +891,63 @@ class Parser {
       return c;
     }
     ThrowError("Parser", "syntax error at or near \"" + (t.k == Tok::END ? std::string("end of input") : t.raw) + "\"");
+  }
+
+  // one bound of a window frame; true: UNBOUNDED PRECEDING / FOLLOWING (which one in *following)
+  bool ParseFrameBound(bool *following, bool *current) {
+    *current = false;
+    if (IsKw("unbounded") && Peek().k == Tok::IDENT && (Peek().s == "preceding" || Peek().s == "following")) {
+      p_++;
+      *following = t_[p_++].s == "following";
+      return true;
+    }
+    if (IsKw("current") && Peek().k == Tok::IDENT && Peek().s == "row") {
+      p_ += 2;
+      *current = true;
+      return false;
+    }
+    ParseExpr();
+    if (!IsKw("preceding") && !IsKw("following")) ThrowError("Parser", "syntax error at or near \"" + Cur().raw + "\"");
+    ThrowError("Not implemented", "a window frame bound of n PRECEDING / n FOLLOWING is not supported by the MI355X backend "
+                                  "(frames from UNBOUNDED PRECEDING to CURRENT ROW or UNBOUNDED FOLLOWING only)");
+  }
+
+  // the parenthesis after OVER
+  std::shared_ptr<OverClause> ParseOver() {
+    auto o = std::make_shared<OverClause>();
+    ExpectOp("(");
+    if (Cur().k == Tok::QIDENT || (Cur().k == Tok::IDENT && !IsKw("partition") && !IsKw("order") && !IsKw("rows") &&
+                                   !IsKw("range") && !IsKw("groups")))
+      ThrowError("Not implemented", "named windows (WINDOW w AS ...) are not supported by the MI355X backend");
+    if (AcceptKw("partition")) {
+      ExpectKw("by");
+      do o->partition.push_back(ParseExpr());
+      while (AcceptOp(","));
+    }
+    if (AcceptKw("order")) {
+      ExpectKw("by");
+      do o->order.push_back(ParseOrderItem());
+      while (AcceptOp(","));
+    }
+    if (IsKw("groups")) ThrowError("Not implemented", "GROUPS window frames are not supported by the MI355X backend");
+    if (IsKw("rows") || IsKw("range")) {
+      o->unit = t_[p_++].s == "rows" ? OverClause::ROWS : OverClause::RANGE;
+      bool following = false, current = false, unbounded;
+      const bool between = AcceptKw("between");
+      unbounded = ParseFrameBound(&following, &current);
+      if (!unbounded || following)
+        ThrowError("Not implemented", "a window frame that starts anywhere but UNBOUNDED PRECEDING is not supported by the "
+                                      "MI355X backend");
+      if (between) {
+        ExpectKw("and");
+        unbounded = ParseFrameBound(&following, &current);
+        if (unbounded && !following) ThrowError("Parser", "a window frame cannot end at UNBOUNDED PRECEDING");
+        o->to_unbounded_following = unbounded;
+      }
+      if (IsKw("exclude")) ThrowError("Not implemented", "EXCLUDE in a window frame is not supported by the MI355X backend");
+    }
+    ExpectOp(")");
+    return o;
   }
 
   ExprPtr ParseCase() {

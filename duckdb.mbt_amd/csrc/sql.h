@@ -5,7 +5,8 @@
 // This parser covers the statements the reference's tests and the benchmark
 // configurations issue: SELECT [DISTINCT] ... FROM {table | range(..) [tbl(col)]
 // | (VALUES ..) t(cols) | (subquery)} {[INNER] JOIN <the same> ON cond}* [WHERE]
-// [GROUP BY] [HAVING] [ORDER BY] [LIMIT/OFFSET] [UNION ALL ...], CREATE TABLE [AS SELECT], INSERT INTO ...
+// [GROUP BY] [HAVING] [ORDER BY] [LIMIT/OFFSET] [UNION ALL ...], window calls f(..) OVER (..)
+// in the select list, CREATE TABLE [AS SELECT], INSERT INTO ...
 // VALUES/SELECT, DROP TABLE.
 #pragma once
 
@@ -27,6 +28,7 @@ struct TypeSpec {
 
 struct Expr;
 typedef std::shared_ptr<Expr> ExprPtr;
+struct OverClause;
 
 struct Expr {
   enum Kind {
@@ -57,6 +59,7 @@ struct Expr {
   int param_index = 0;       // 1-based
   std::string alias;
   std::string text;          // original text for column naming
+  std::shared_ptr<OverClause> over;  // FUNC: f(args) OVER (...), a window call
 };
 
 struct TableRef {
@@ -76,6 +79,15 @@ struct OrderItem {
   ExprPtr expr;
   bool desc = false;
   int nulls_first = -1;  // -1 default
+};
+
+// f(args) OVER ([PARTITION BY ...] [ORDER BY ...] [frame]).  The parser only
+// lets through frames that start at UNBOUNDED PRECEDING.
+struct OverClause {
+  std::vector<ExprPtr> partition;
+  std::vector<OrderItem> order;
+  enum Unit { NO_FRAME, ROWS, RANGE } unit = NO_FRAME;
+  bool to_unbounded_following = false;  // the frame's end; else CURRENT ROW
 };
 
 struct Select {
