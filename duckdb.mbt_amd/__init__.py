@@ -91,6 +91,7 @@ _sig("duckdb_mbx_shard_stats", _I, _P, ctypes.POINTER(ctypes.c_int64), ctypes.PO
 _sig("duckdb_mbx_engine_stats", _I, _P, ctypes.POINTER(ctypes.c_int64))
 _sig("duckdb_mbx_result_tail_stats", _I, _P, ctypes.POINTER(ctypes.c_int64))
 _sig("duckdb_mbx_tail_wait_stats", _I, _P, ctypes.POINTER(ctypes.c_int64))
+_sig("duckdb_mbx_scan_hist_host_stats", _I, _P, ctypes.POINTER(ctypes.c_int64), ctypes.c_char_p, ctypes.c_int32)
 _sig("duckdb_mbx_shard_timings", _I, _P, ctypes.POINTER(ctypes.c_double), _I)
 _sig("duckdb_mbx_shard_partial", _P, _P, _I)
 _sig("duckdb_mbx_rccl_stats", _I, _P, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_double))
@@ -648,6 +649,16 @@ class Connection:
         out = (ctypes.c_int64 * 4)()
         lib.duckdb_mbx_tail_wait_stats(self._h, out)
         return {"polled": out[0], "blocked": out[1], "wait_ns": out[2], "event_pairs": out[3]}
+
+    def scan_hist_host_stats(self) -> dict:
+        """Range aggregates answered on the host with no launch
+        (mbx_scan_hist_host; extension): statements answered, histogram mirror
+        fetches, statements that wanted the host answer and took the device
+        path, and why the last of those did."""
+        out = (ctypes.c_int64 * 3)()
+        why = ctypes.create_string_buffer(128)
+        lib.duckdb_mbx_scan_hist_host_stats(self._h, out, why, 128)
+        return {"answered": out[0], "fetches": out[1], "declined": out[2], "last_reason": why.value.decode()}
 
     def shard_timings(self) -> list:
         """The last sharded dispatch, per shard (extension): device and the us

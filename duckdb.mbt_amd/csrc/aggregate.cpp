@@ -6,6 +6,7 @@
 #include <functional>
 #include <map>
 
+#include "emit_cell.h"
 #include "exec.h"
 #include "jit.h"
 #include "vm_compile.h"
@@ -82,11 +83,37 @@ static StatementShape ShapeOf(const Engine &e, const BoundSelect &s) {
   return h;
 }
 
+// Whether the one-row relation of s's aggregates takes the result tail, and
+// where its cells lie in the mapped buffer (mark.off): every column's physical
+// type is its aggregate's, and AllocOut gives every one a validity bitmap.
+static ResultTailChoice OneRowTail(const Engine &e, const BoundSelect &s, ResultTailMark &mark) {
+  const int na = (int)s.aggs.size();
+  ResultTailFacts f;
+  f.enabled = e.result_tail;
+  f.shape = ShapeOf(e, s);
+  f.grouped = !s.groups.empty();
+  f.ncols = na;
+  f.max_cols = EMIT_MAX_AGGS;
+  f.mapped_bytes = Engine::kMappedBytes;
+  f.max_segs = HOSTCOPY_MAX;
+  f.no_hostcopy = Knob("MBX_NO_HOSTCOPY");
+  int cell[EMIT_MAX_AGGS];
+  bool has_valid[EMIT_MAX_AGGS];
+  for (int j = 0; j < na && j < EMIT_MAX_AGGS; j++) {
+    const Phys p = PhysOf(s.aggs[j].type);
+    f.varchar |= p == P_STR;
+    cell[j] = PhysSize(p);
+    has_valid[j] = true;
+  }
+  if (na <= EMIT_MAX_AGGS) f.need = ResultBufferLayout((size_t)na, cell, has_valid, 1, 1, false, mark.off);
+  return ResultTailDecide(f);
+}
+
 // The one-row relation of an aggregate without GROUP BY, emitted from the
 // states (and, for the fused scans, the workgroups' partials).
 // launch: what runs the emit (EmitAggRelation unless the caller's own last
 // kernel takes the descriptor).  Where the statement allows
-// (ResultTailDecide), the emit also stores the row in the mapped buffer and the
+// (OneRowTail), the emit also stores the row in the mapped buffer and the
 // relation says so (DRel::tail), so ToHost has nothing left to copy.
 static DRel EmitOneRow(Engine &e, const BoundSelect &s, const unsigned long long *cstar, const EmitInOf &in_of,
                        const dev::AggPartial *partials = nullptr, int npartials = 0,
@@ -97,27 +124,8 @@ static DRel EmitOneRow(Engine &e, const BoundSelect &s, const unsigned long long
   D.partials = partials;
   D.npartials = npartials;
   EmitAggCols(e, s, 1, in_of, D, out);
-  ResultTailFacts f;
-  f.enabled = e.result_tail;
-  f.shape = ShapeOf(e, s);
-  f.grouped = !s.groups.empty();
-  f.ncols = D.nagg;
-  f.max_cols = EMIT_MAX_AGGS;
-  f.mapped_bytes = Engine::kMappedBytes;
-  f.max_segs = HOSTCOPY_MAX;
-  f.no_hostcopy = Knob("MBX_NO_HOSTCOPY");
-  int cell[EMIT_MAX_AGGS];
-  bool has_valid[EMIT_MAX_AGGS];
-  for (int j = 0; j < D.nagg && j < EMIT_MAX_AGGS; j++) {
-    f.varchar |= out.cols[j].phys == P_STR;
-    cell[j] = PhysSize(out.cols[j].phys);
-    has_valid[j] = out.cols[j].validity != nullptr;
-  }
   auto mark = std::make_shared<ResultTailMark>();
-  if (D.nagg <= EMIT_MAX_AGGS) f.need = ResultBufferLayout((size_t)D.nagg, cell, has_valid, 1, 1, false, mark->off);
-  bool bitmaps = true;  // (the emit writes every aggregate's validity word: AllocOut gave each a bitmap)
-  for (int j = 0; j < D.nagg && j < EMIT_MAX_AGGS; j++) bitmaps &= has_valid[j];
-  if (bitmaps && ResultTailDecide(f).take) {
+  if (OneRowTail(e, s, *mark).take) {
     mark->serial = e.tail_serial;
     mark->ncols = (size_t)D.nagg;
     for (int j = 0; j < D.nagg; j++) {
@@ -137,6 +145,118 @@ static DRel EmitOneRow(Engine &e, const BoundSelect &s, const unsigned long long
   if (launch) launch(D);
   else dev::EmitAggRelation(D, e.stream);
   return out;
+}
+
+// ---- the host answer (mbx_scan_hist_host) ---------------------------------
+// A range aggregate that the code histogram answers is a function of at most
+// 2 KiB of counters that change only when the table is written.  Where its row
+// is the statement's own result (OneRowTail), the host folds a mirror of the
+// counters with the functions the kernel runs (scan_hist.h), forms the cells
+// with the emit's own definition (emit_cell.h) and stores them where the emit
+// would have: nothing is launched and ToHost has nothing to wait for.
+
+// the state emit_cell_int reads, from the fold's values
+struct HostCellState {
+  unsigned long long count, sum_lo;
+  long long sum_hi, min_i, max_i;
+};
+
+// c's histogram mirror, fetched if it is none or describes another state of
+// the column: one copy behind the encode that counted the rows, one wait.
+static const uint64_t *HistMirror(Engine &e, const DevColumn &c) {
+  if (!c.HistMirrorValid()) {
+    const size_t bytes = (size_t)ScanHistBytes(c.code_planes);
+    if (!e.EnsurePinned(bytes)) return nullptr;
+    HIPCHK(hipMemcpyAsync(e.h_pinned, c.code_hist, bytes, hipMemcpyDeviceToHost, e.stream));
+    HIPCHK(hipStreamSynchronize(e.stream));
+    c.hist_mirror.resize(bytes / 8);
+    memcpy(c.hist_mirror.data(), e.h_pinned, bytes);
+    c.hist_mirror_rows = c.code_rows;
+    c.hist_mirror_base = c.code_base;
+    c.hist_mirror_planes = c.code_planes;
+    e.hist_host.fetches++;
+  }
+  return c.hist_mirror.data();
+}
+
+// The one-row relation of s's aggregates from v, stored by the host in the
+// mapped buffer in the tail's layout (mark, from OneRowTail) with a zero error
+// word: nothing of this statement ran on the device.  The relation's device
+// columns are allocated, as every relation's are, and never written: ToHost
+// takes the mark or raises.
+static DRel HostEmitOneRow(Engine &e, const BoundSelect &s, const ScanHistValues &v,
+                           const std::shared_ptr<ResultTailMark> &mark) {
+  const int na = (int)s.aggs.size();
+  HostCellState S;
+  S.count = v.cnt;
+  S.sum_lo = v.slo;
+  S.sum_hi = v.shi;
+  S.min_i = v.mn;
+  S.max_i = v.mx;
+  DRel out;
+  out.n = 1;
+  mark->serial = e.tail_serial;
+  mark->ncols = (size_t)na;
+  mark->host_filled = true;
+  for (int j = 0; j < na; j++) {
+    DCol oc = AllocOut(e, s.aggs[j].type, 1, true, false);
+    const dev::EmitAgg A = EmitFor(s.aggs[j], VC_I64, nullptr, oc);
+    int64_t lo, hi;
+    const bool valid = dev::emit_cell_int((int)A.kind, (int)A.avg_scale, S.count, &S, lo, hi);
+    dev::store_phys(e.h_mapped + mark->off[j].data_off, A.out_phys, 0, lo, hi);
+    const uint64_t vw = valid ? 1ull : 0ull;
+    memcpy(e.h_mapped + mark->off[j].valid_off, &vw, 8);
+    mark->data[j] = oc.data;
+    mark->valid[j] = oc.validity;
+    out.cols.push_back(oc);
+  }
+  const int32_t no_err = 0;
+  memcpy(e.h_mapped, &no_err, 4);
+  out.tail = mark;
+  e.hist_host.answered++;
+  return out;
+}
+
+// Answers s on the host where the option and the floor allow it, the
+// statement takes the tail and, with hist_col, that column's mirror is valid
+// after at most one fetch: from the fold of the mirror's counters over
+// [clo, chi], or without hist_col from `known` rows that pass (the zone map
+// rules every row out; every row passes and only their number is asked).
+// false: the caller's device path answers, and the counters say why.
+static bool HostAnswer(Engine &e, const BoundSelect &s, int64_t n, const DevColumn *hist_col, uint32_t clo,
+                       uint32_t chi, uint64_t known, DRel &out) {
+  if (!e.scan_hist_host || n < e.scan_hist_host_min_rows) return false;  // (not wanted: nothing is counted)
+  auto mark = std::make_shared<ResultTailMark>();
+  const ResultTailChoice ch = OneRowTail(e, s, *mark);
+  if (!ch.take) {
+    e.hist_host.declined++;
+    e.hist_host.last_reason = ch.reason;
+    return false;
+  }
+  // ToHost takes the mark only for the relation's own columns, each once and in
+  // order; the emit's row can still be copied where it does not, this one cannot
+  bool own_cols = s.outputs.size() == s.aggs.size() && VisibleCols(s) == s.aggs.size();
+  for (size_t i = 0; own_cols && i < s.outputs.size(); i++)
+    own_cols = s.outputs[i]->kind == BExpr::COL && s.outputs[i]->col == (int)i;
+  if (!own_cols) {
+    e.hist_host.declined++;
+    e.hist_host.last_reason = "the outputs are not the aggregates, each once and in order";
+    return false;
+  }
+  ScanHistFold f = ScanHistFold{known, 0, INT32_MAX, -1};
+  int64_t base = 0;
+  if (hist_col) {
+    const uint64_t *h = HistMirror(e, *hist_col);
+    if (!h) {
+      e.hist_host.declined++;
+      e.hist_host.last_reason = "no page-locked memory for the mirror's fetch";
+      return false;
+    }
+    f = ScanHistFoldRange(h, hist_col->code_planes, clo, chi);
+    base = hist_col->code_base;
+  }
+  out = HostEmitOneRow(e, s, ScanHistValuesOf(f, base), mark);
+  return true;
 }
 
 DRel EmitGlobalStates(Engine &e, const BoundSelect &s, const unsigned long long *cstar, dev::AggState *states) {
@@ -1124,6 +1244,10 @@ static bool ScanAggregate(Engine &e, const DRel &src, const BoundSelect &s, DRel
           PlanScanPlanes(tc->code_planes, (i128)tc->code_base, tc->imax, (int64_t)lo, (int64_t)hi, A != nullptr);
       // the column's code histogram answers what the planes would (scan_hist.h)
       const bool by_hist = e.scan_hist && tc->code_hist && !pp.empty && pp.planes > 0;
+      // the host answers what needs no pass over the rows (no launch, no profile entry)
+      if ((pp.empty || pp.planes == 0 || by_hist) &&
+          HostAnswer(e, s, src.n, by_hist ? tc : nullptr, pp.clo, pp.chi, pp.empty ? 0 : (uint64_t)src.n, out))
+        return true;
       ProfScope ps(e, "filter_agg",
                    pp.empty  ? 0
                    : by_hist ? (double)ScanHistBytes(tc->code_planes)
@@ -1147,6 +1271,7 @@ static bool ScanAggregate(Engine &e, const DRel &src, const BoundSelect &s, DRel
       }
     } else if (by_codes) {
       const ScanCodeRange cr = PlanScanFieldRange(tc->code_fields, (i128)tc->code_base, tc->imax, (int64_t)lo, (int64_t)hi);
+      if (cr.empty && HostAnswer(e, s, src.n, nullptr, 0, 0, 0, out)) return true;
       if (cr.empty) {
         // the zone map rules every row out: no scan (the entry keeps the
         // profile at one filter_agg per statement, with nothing read)
@@ -1173,6 +1298,7 @@ static bool ScanAggregate(Engine &e, const DRel &src, const BoundSelect &s, DRel
                                        e.d_partials);
     } else {
       // COUNT(*) without predicate: the row count is known
+      if (HostAnswer(e, s, src.n, nullptr, 0, 0, (uint64_t)src.n, out)) return true;
       known_count();
     }
   }

@@ -13,6 +13,7 @@
 #include <limits>
 #include <set>
 
+#include "emit_cell.h"
 #include "engine.h"
 #include "plan.h"
 #include "str_match.h"
@@ -185,23 +186,8 @@ static bool DoubleToI128(double x, i128 *out) {
   return true;
 }
 
-// int128 -> double, correctly rounded (one rounding of the 128-bit magnitude);
-// the device uses the same steps (i128_to_double in vm_device.h)
-static double I128ToDouble(i128 v) {
-  bool neg = v < 0;
-  u128 m = neg ? (u128)0 - (u128)v : (u128)v;
-  uint64_t hi = (uint64_t)(m >> 64), lo = (uint64_t)m;
-  double d;
-  if (hi == 0) {
-    d = (double)lo;
-  } else {
-    int sh = __builtin_clzll(hi);
-    uint64_t top = sh ? (hi << sh) | (lo >> (64 - sh)) : hi;
-    if (lo << sh) top |= 1;  // sticky bit: the discarded low bits only matter as "non-zero"
-    d = std::ldexp((double)top, 64 - sh);
-  }
-  return neg ? -d : d;
-}
+// int128 -> double, correctly rounded: the device's own function (emit_cell.h)
+static double I128ToDouble(i128 v) { return dev::i128_to_double(v); }
 
 Value CastValue(const Value &v, const LogicalType &to, bool try_cast) {
   Value out;

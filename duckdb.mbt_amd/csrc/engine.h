@@ -67,6 +67,23 @@ struct DevColumn {
   // is answered from it.
   void *code_hist = nullptr;
   std::shared_ptr<void> code_hist_owner;
+  // Host mirror of the histogram (mbx_scan_hist_host): the counters as they
+  // stood at hist_mirror_rows rows with the base hist_mirror_base and
+  // hist_mirror_planes bits per code; -1 rows: none.  Fetched by the first
+  // statement that could answer from it and finds none (one copy and one
+  // stream wait, aggregate.cpp), and usable only while those three equal
+  // code_rows, code_base and code_planes.  UpdateScanCodes, the only writer of
+  // the histogram, marks it "none" wherever it drops, rebuilds, extends or
+  // regrows the histogram.  A cache of device state, so a statement that reads
+  // the column (const) may fill it.
+  mutable std::vector<uint64_t> hist_mirror;
+  mutable int64_t hist_mirror_rows = -1, hist_mirror_base = 0;
+  mutable int hist_mirror_planes = 0;
+  void DropHistMirror() { hist_mirror_rows = -1; }
+  bool HistMirrorValid() const {
+    return hist_mirror_rows >= 0 && code_hist && hist_mirror_rows == code_rows && hist_mirror_base == code_base &&
+           hist_mirror_planes == code_planes;
+  }
 };
 
 struct Table {
@@ -206,6 +223,18 @@ struct Options {
   // (the default is the planes floor's: below it even a scan of every plane
   // streams in under 2 us, and the query is launch-bound either way)
   int64_t scan_hist_min_rows = (int64_t)1 << 24;
+  // "mbx_scan_hist_host": a range aggregate the histogram answers, whose row
+  // is the statement's own result (result_tail.h), is answered on the host
+  // from a mirror of the counters, with no launch; so are the three shapes that
+  // need no counters (the zone map rules every row out, every row passes and
+  // only the count is asked, COUNT(*) without predicate).  false: the
+  // histogram kernel answers, as on shard engines and off the tail
+  bool scan_hist_host = true;
+  // "mbx_scan_hist_host_min_rows": tables below this many rows keep the device
+  // path (the host answer is faster at any size; the floor keeps the device
+  // path, which shard engines and statements off the tail still run, under the
+  // small tables of the tests that pin its ticket, profile and counters)
+  int64_t scan_hist_host_min_rows = (int64_t)1 << 24;
   // "mbx_result_tail": the kernel that emits the one row of an aggregate
   // without GROUP BY also stores it in the host's mapped buffer where that row
   // is the statement's result (result_tail.h), so no copy kernel follows
@@ -395,6 +424,10 @@ void ResultTailCounters(const Connection &c, int64_t out[2]);
 // {statements whose result tail the host polled, statements that blocked on
 // the stream for it, ns spent in that wait, profile event pairs made}
 void TailWaitCounters(const Connection &c, int64_t out[4]);
+// {statements answered on the host from a histogram mirror or the zone map
+// (mbx_scan_hist_host), mirror fetches, statements that wanted the host answer
+// and took the device path}; returns why the last of those did ("": none yet)
+const char *ScanHistHostCounters(const Connection &c, int64_t out[3]);
 // reads the kernel times of statements whose profile is still pending into
 // last_profile and profile_history (before either is looked at)
 void SettleConnProfile(Connection &c);

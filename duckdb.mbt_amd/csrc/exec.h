@@ -185,6 +185,17 @@ struct Engine {
   // mbx_scan_hist / mbx_scan_hist_min_rows (set by Eng)
   bool scan_codes = true, scan_hist = true;
   int64_t scan_hist_min_rows = 0;
+  // mbx_scan_hist_host / mbx_scan_hist_host_min_rows (set by Eng), and what
+  // became of the statements they cover (duckdb_mbx_scan_hist_host_stats):
+  // answered on the host with no launch; fetches of a column's histogram
+  // mirror; statements that wanted the host answer and took the device path,
+  // with the reason of the last one
+  bool scan_hist_host = true;
+  int64_t scan_hist_host_min_rows = 0;
+  struct ScanHistHostStats {
+    int64_t answered = 0, fetches = 0, declined = 0;
+    const char *last_reason = "";
+  } hist_host;
   int64_t scan_codes_min_rows = 0, scan_codes_bits_min_rows = 0, scan_codes_planes_min_rows = 0;
   bool profile = false;
   std::vector<ProfEvent> events;
@@ -316,6 +327,10 @@ struct DCol {
 struct ResultTailMark {
   uint64_t serial = 0;  // Engine::tail_serial when it was made
   uint64_t ticket = 0;  // what the emit stores behind the row (Engine::tail_ticket)
+  // the host itself stored the row and a zero error word (a histogram range
+  // aggregate answered from the mirror): no kernel ran, there is no ticket to
+  // wait for, and the relation's device columns were never written
+  bool host_filled = false;
   size_t ncols = 0;
   const void *data[EMIT_MAX_AGGS];
   const void *valid[EMIT_MAX_AGGS];

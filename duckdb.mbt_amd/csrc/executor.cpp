@@ -130,6 +130,8 @@ Engine &Eng(Connection &c) {
   e.scan_codes_planes_min_rows = c.opts.scan_codes_planes_min_rows;
   e.scan_hist = c.opts.scan_hist;
   e.scan_hist_min_rows = c.opts.scan_hist_min_rows;
+  e.scan_hist_host = c.opts.scan_hist_host;
+  e.scan_hist_host_min_rows = c.opts.scan_hist_host_min_rows;
   e.result_tail = c.opts.result_tail;
   e.tail_spin_ns = c.opts.tail_spin_us * 1000;
   SettlePending(e);  // a statement never sees a column before its appended stats
@@ -1412,6 +1414,11 @@ static ResultPtr ToHostPinned(Engine &e, const DRel &r, const std::vector<std::s
   for (size_t c = 0; tail && c < ncols; c++)
     tail = r.cols[c].data == r.tail->data[c] && r.cols[c].validity == r.tail->valid[c] &&
            lay[c].data_off == r.tail->off[c].data_off && lay[c].valid_off == r.tail->off[c].valid_off;
+  // a relation the host itself filled (the histogram's host answer) is in the
+  // mapped buffer and nowhere else: its device columns were never written
+  const bool host_filled = r.tail && r.tail->host_filled;
+  if (host_filled && !tail)
+    ThrowError("Internal", "a host-filled relation reached the host by another way than its tail");
   if (count_dev && !mapped) return nullptr;
   if (!mapped && !e.EnsurePinned(need)) return nullptr;
   uint8_t *const H = mapped ? e.h_mapped : e.h_pinned;
@@ -1469,14 +1476,17 @@ static ResultPtr ToHostPinned(Engine &e, const DRel &r, const std::vector<std::s
     at += ((size_t)j.total + 63) & ~(size_t)63;
   }
   if (tail) {
-    e.tail_results++;
+    if (!host_filled) e.tail_results++;  // (the host's own rows: duckdb_mbx_scan_hist_host_stats)
   } else if (mapped) {
     hd.err_src = e.d_err;
     hd.err_dst = (int32_t *)H;
     dev::HostCopy(hd, e.stream);
     e.hostcopy_results++;
   }
-  if (tail) {
+  if (host_filled) {
+    // nothing ran, so there is nothing to wait for: no ticket was taken, and
+    // the stream is not draining on this statement's account
+  } else if (tail) {
     // the row's ticket, not the stream: the emit stored it last, with release
     // (tail_wait.h); the error word and the cells are read only after it
     const uint64_t *tk = (const uint64_t *)(H + kTailTicketOffset);
@@ -1562,6 +1572,8 @@ ResultPtr ToHost(Engine &e, const DRel &r, const std::vector<std::string> &names
     ResultPtr p = ToHostPinned(e, r, names, ncols, start, n, text);
     if (p) return p;
   }
+  if (r.tail && r.tail->host_filled)
+    ThrowError("Internal", "a host-filled relation reached the host by another way than its tail");
   auto res = std::make_shared<MaterializedResult>();
   res->nrows = n;
   for (size_t c = 0; c < ncols; c++) {
@@ -2057,6 +2069,15 @@ void TailWaitCounters(const Connection &c, int64_t out[4]) {
     out[3] += (int64_t)c.engine->ev_pool.size();
   }
   for (auto &sc : c.shards) TailWaitCounters(*sc, out);
+}
+
+const char *ScanHistHostCounters(const Connection &c, int64_t out[3]) {
+  // (shard engines take no tail and so never answer on the host: the connection's own engine only)
+  if (!c.engine) return "";
+  out[0] += c.engine->hist_host.answered;
+  out[1] += c.engine->hist_host.fetches;
+  out[2] += c.engine->hist_host.declined;
+  return c.engine->hist_host.last_reason;
 }
 
 void SettleConnProfile(Connection &c) {

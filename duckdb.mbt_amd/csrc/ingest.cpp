@@ -132,6 +132,7 @@ void UpdateScanCodes(Engine &e, DevColumn &c, int64_t nrows) {
   if (!hist) {  // the histogram goes with the plane image, or with the option
     c.code_hist = nullptr;
     c.code_hist_owner.reset();
+    c.DropHistMirror();
   }
   if (!f && !pb) {
     c.codes = nullptr;
@@ -147,6 +148,9 @@ void UpdateScanCodes(Engine &e, DevColumn &c, int64_t nrows) {
                       c.code_rows <= nrows && (!hist || c.code_hist);
   const int64_t begin = extend ? c.code_rows : 0;
   if (begin == nrows) return;
+  // from here on the histogram is rebuilt (zeroed and recounted), or extended
+  // or regrown by the appended rows: the host mirror no longer describes it
+  c.DropHistMirror();
   if (!extend || c.code_cap < nrows) {
     const int64_t cap = std::max<int64_t>(nrows, c.capacity);
     const int64_t bytes = pb ? ScanPlaneBufferBytes(pb, cap) : (ScanCodeWords(f, cap) * 4 + 255) & ~(int64_t)255;

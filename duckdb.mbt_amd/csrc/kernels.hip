@@ -2717,36 +2717,22 @@ __global__ void slot_scatter_kernel(const int32_t *flag, const int32_t *pos, int
 // (not read for COUNT(*)); false: the cell is NULL.
 __device__ __forceinline__ bool emit_cell(const EmitAgg &A, unsigned long long cstar, const AggState *S, int64_t &lo,
                                           int64_t &hi) {
+  // the integer class (the counts whatever the class) is emit_cell.h's, which
+  // the host compiles too; floating-point states and 128-bit MIN / MAX are here
+  const bool minmax = A.kind == 3 || A.kind == 4;
+  if (A.kind <= 1 || (A.in_class != VC_F64 && !(minmax && A.wide_minmax)))
+    return emit_cell_int(A.kind, A.avg_scale, cstar, S, lo, hi);
   lo = 0;
   hi = 0;
+  if (!S->count) return false;
   switch (A.kind) {
-    case 0: /*COUNT_STAR*/ lo = (int64_t)cstar; return true;
-    case 1: /*COUNT*/ lo = (int64_t)S->count; return true;
-    case 2: /*SUM*/
-      if (!S->count) return false;
-      if (A.in_class == VC_F64) lo = __double_as_longlong(S->sum_f);
-      else { lo = (int64_t)S->sum_lo; hi = S->sum_hi; }
-      return true;
+    case 2: /*SUM*/ lo = f64_bits(S->sum_f); return true;
     case 3: /*MIN*/
     case 4: /*MAX*/
-      if (!S->count) return false;
-      if (A.in_class == VC_F64) lo = __double_as_longlong(f64_unorder(A.kind == 3 ? S->min_f : S->max_f));
-      else if (A.wide_minmax) { lo = (int64_t)(A.kind == 3 ? S->min_f : S->max_f); hi = A.kind == 3 ? S->min_i : S->max_i; }
-      else { lo = A.kind == 3 ? S->min_i : S->max_i; hi = lo >> 63; }
+      if (A.in_class == VC_F64) lo = f64_bits(f64_unorder(A.kind == 3 ? S->min_f : S->max_f));
+      else { lo = (int64_t)(A.kind == 3 ? S->min_f : S->max_f); hi = A.kind == 3 ? S->min_i : S->max_i; }
       return true;
-    default: /*AVG*/ {
-      if (!S->count) return false;
-      double v;
-      if (A.in_class == VC_F64) v = S->sum_f / (double)S->count;
-      else {
-        double sum = i128_to_double(mk128((int64_t)S->sum_lo, S->sum_hi));
-        double div = (double)S->count;
-        for (int k = 0; k < A.avg_scale; k++) div *= 10.0;
-        v = sum / div;
-      }
-      lo = __double_as_longlong(v);
-      return true;
-    }
+    default: /*AVG*/ lo = f64_bits(S->sum_f / (double)S->count); return true;
   }
 }
 

@@ -466,6 +466,12 @@ int32_t duckdb_mb_config_set(duckdb_mb_config *c, moonbit_bytes_t key, moonbit_b
   } else if (kl == "mbx_scan_hist_min_rows") {
     ok = IsInt(v, &x) && x >= 0;
     if (ok) c->opts.scan_hist_min_rows = x;
+  } else if (kl == "mbx_scan_hist_host") {
+    ok = v == "true" || v == "1" || v == "false" || v == "0";
+    if (ok) c->opts.scan_hist_host = v == "true" || v == "1";
+  } else if (kl == "mbx_scan_hist_host_min_rows") {
+    ok = IsInt(v, &x) && x >= 0;
+    if (ok) c->opts.scan_hist_host_min_rows = x;
   } else if (kl == "mbx_result_tail") {
     ok = v == "true" || v == "1" || v == "false" || v == "0";
     if (ok) c->opts.result_tail = v == "true" || v == "1";
@@ -1961,6 +1967,17 @@ int32_t duckdb_mbx_tail_wait_stats(duckdb_mb_connection *h, int64_t *out4) {
   out4[0] = out4[1] = out4[2] = out4[3] = 0;
   TailWaitCounters(h->conn, out4);
   return 4;
+}
+
+// out3 = {statements answered on the host (mbx_scan_hist_host), histogram
+// mirror fetches, statements that wanted the host answer and took the device
+// path}; reason (reason_len bytes, may be null): why the last of those did.
+int32_t duckdb_mbx_scan_hist_host_stats(duckdb_mb_connection *h, int64_t *out3, char *reason, int32_t reason_len) {
+  if (!h || !out3) return 0;
+  out3[0] = out3[1] = out3[2] = 0;
+  const char *why = ScanHistHostCounters(h->conn, out3);
+  if (reason && reason_len > 0) snprintf(reason, (size_t)reason_len, "%s", why);
+  return 3;
 }
 
 int32_t duckdb_mbx_result_raw(duckdb_mb_result *r, int32_t col, int32_t row, void *out, int32_t out_len) {

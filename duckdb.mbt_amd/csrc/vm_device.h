@@ -7,6 +7,7 @@
 #pragma once
 #include <stdint.h>
 
+#include "emit_cell.h"
 #include "phys.h"
 #include "vm.h"
 
@@ -47,25 +48,7 @@ __device__ __forceinline__ void load_phys(const void *data, int phys, int64_t ro
   }
 }
 
-__device__ __forceinline__ void store_phys(void *data, int phys, int64_t row, int64_t lo, int64_t hi) {
-  switch (phys) {
-    case P_U8: ((uint8_t *)data)[row] = (uint8_t)lo; break;
-    case P_I8: ((int8_t *)data)[row] = (int8_t)lo; break;
-    case P_I16: ((int16_t *)data)[row] = (int16_t)lo; break;
-    case P_U16: ((uint16_t *)data)[row] = (uint16_t)lo; break;
-    case P_I32: ((int32_t *)data)[row] = (int32_t)lo; break;
-    case P_U32: ((uint32_t *)data)[row] = (uint32_t)lo; break;
-    case P_I64: case P_U64: case P_F64: case P_STR: ((int64_t *)data)[row] = lo; break;
-    case P_I128: {
-      int64_t *p = (int64_t *)data + 2 * row;
-      p[0] = lo;
-      p[1] = hi;
-      break;
-    }
-    case P_F32: ((float *)data)[row] = (float)__longlong_as_double(lo); break;
-    default: break;
-  }
-}
+// store_phys: emit_cell.h
 
 __device__ __forceinline__ i128 mk128(int64_t lo, int64_t hi) { return (i128)(((u128)(uint64_t)hi << 64) | (uint64_t)lo); }
 __device__ __forceinline__ void sp128(i128 v, int64_t &lo, int64_t &hi) {
@@ -131,22 +114,7 @@ __device__ __forceinline__ int64_t pow10_64(int k) {
   return r;
 }
 
-// int128 -> double through the magnitude, correctly rounded: the top 64
-// significant bits with a sticky bit for the rest are rounded once, and the
-// power-of-two scaling is exact.  The host folder does the same steps
-// (I128ToDouble in binder.cpp).
-__device__ __forceinline__ double u128_to_double(u128 m) {
-  uint64_t hi = (uint64_t)(m >> 64), lo = (uint64_t)m;
-  if (hi == 0) return (double)lo;
-  int sh = __clzll((long long)hi);
-  uint64_t top = sh ? (hi << sh) | (lo >> (64 - sh)) : hi;
-  if (lo << sh) top |= 1;
-  return ldexp((double)top, 64 - sh);
-}
-__device__ __forceinline__ double i128_to_double(i128 v) {
-  if (v < 0) return -u128_to_double((u128)0 - (u128)v);
-  return u128_to_double((u128)v);
-}
+// u128_to_double, i128_to_double (int128 -> double, correctly rounded): emit_cell.h
 
 __device__ __forceinline__ uint64_t splitmix64(uint64_t z) {
   z += 0x9E3779B97F4A7C15ull;

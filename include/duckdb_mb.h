@@ -323,6 +323,16 @@ int32_t duckdb_mbx_result_tail_stats(duckdb_mb_connection *connection, int64_t *
  * event pairs the engines hold}.  Returns 4 (0: no handle). */
 int32_t duckdb_mbx_tail_wait_stats(duckdb_mb_connection *connection, int64_t *out4);
 
+/* Range aggregates answered on the host with no launch (mbx_scan_hist_host),
+ * on the connection's own engine: out3 = {statements answered from a column's
+ * histogram mirror or, where no counter is needed, from the zone map and the
+ * row count; mirror fetches (one device-to-host copy and one stream wait each);
+ * statements that wanted the host answer and took the device path}.  reason
+ * (may be null) receives, NUL-terminated within reason_len bytes, why the last
+ * statement of the third kind did.  Returns 3 (0: no handle). */
+int32_t duckdb_mbx_scan_hist_host_stats(duckdb_mb_connection *connection, int64_t *out3, char *reason,
+                                        int32_t reason_len);
+
 /* The last sharded dispatch, per shard i: out[4 i .. 4 i + 3] = {device,
  * wake_us, launch_us, done_us}, us since the dispatch began (the worker took
  * the job; its plan and launches were queued; its result reached the host:
