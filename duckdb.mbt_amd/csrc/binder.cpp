@@ -67,10 +67,18 @@ static BExprPtr MkFunc(BOp op, const LogicalType &t, std::vector<BExprPtr> ch) {
 }
 
 bool IsConstTree(const BExpr &e) {
-  if (e.kind == BExpr::COL) return false;
+  if (e.kind == BExpr::COL || e.sub) return false;  // a membership leaf reads its subquery's rows
   for (auto &c : e.ch)
     if (!IsConstTree(*c)) return false;
   return true;
+}
+
+bool HasMembership(const BExprPtr &e) {
+  if (!e) return false;
+  if (e->sub) return true;
+  for (auto &c : e->ch)
+    if (HasMembership(c)) return true;
+  return false;
 }
 
 static BExprPtr Fold(BExprPtr e) {
@@ -710,6 +718,10 @@ static const char *OpSym(BOp op) {
   }
 }
 
+// EXPLAIN numbers the membership leaves of a statement (ExplainSelect); a leaf
+// printed outside one has no number
+static thread_local std::map<const BExpr *, int> *g_subq_ids = nullptr;
+
 std::string ExprToString(const BExpr &e) {
   switch (e.kind) {
     case BExpr::CONST:
@@ -739,6 +751,11 @@ std::string ExprToString(const BExpr &e) {
     case B_LIKE:
       return "(" + ExprToString(*e.ch[0]) + " LIKE " + ExprToString(*e.ch[1]) +
              (e.ch.size() > 2 ? " ESCAPE " + ExprToString(*e.ch[2]) : "") + ")";
+    case B_IN_SUBQUERY: {
+      s = "(" + ExprToString(*e.ch[0]) + " IN SUBQUERY";
+      if (g_subq_ids && g_subq_ids->count(&e)) s += " " + std::to_string((*g_subq_ids)[&e]);
+      return s + ")";
+    }
     case B_DISTINCT: return "(" + ExprToString(*e.ch[0]) + " IS DISTINCT FROM " + ExprToString(*e.ch[1]) + ")";
     case B_NOT_DISTINCT: return "(" + ExprToString(*e.ch[0]) + " IS NOT DISTINCT FROM " + ExprToString(*e.ch[1]) + ")";
     default:
@@ -759,7 +776,8 @@ static bool BoundEq(const BExpr &a, const BExpr &b) {
   if (a.op != b.op || a.ch.size() != b.ch.size()) return false;
   for (size_t i = 0; i < a.ch.size(); i++)
     if (!BoundEq(*a.ch[i], *b.ch[i])) return false;
-  return true;
+  if ((bool)a.sub != (bool)b.sub) return false;
+  return !a.sub || a.sub == b.sub || BoundSelectEq(*a.sub, *b.sub);
 }
 
 // ---------------------------------------------------------------------------
@@ -774,6 +792,13 @@ struct ScopeCol {
 
 // BindSelectCapture: the constant node of every parameter reference, in bind order
 static thread_local std::vector<std::pair<BExprPtr, int>> *g_param_nodes = nullptr;
+
+// What a membership subquery is bound with and against: the catalog of the
+// statement being bound (BindSelect), and the scopes of the selects that
+// enclose the subquery, innermost last -- a name found only there is a
+// correlated reference
+static thread_local Catalog *g_bind_cat = nullptr;
+static thread_local std::vector<const std::vector<ScopeCol> *> g_outer_scopes;
 
 struct BindCtx {
   std::vector<ScopeCol> scope;
@@ -854,6 +879,8 @@ bool ContainsWindow(const Expr &e) {
 }
 
 BExprPtr BindExpr(const Expr &e, BindCtx &ctx);
+BExprPtr BindMembership(const Expr &e, BindCtx &ctx);
+bool IsStrLit(const Expr &e);
 
 BExprPtr BindCompare(BOp op, BExprPtr l, BExprPtr r, bool l_strlit = false, bool r_strlit = false) {
   LogicalType t;
@@ -1212,6 +1239,75 @@ BExprPtr BindExprInner(const Expr &e, BindCtx &ctx);
 // becomes a reference to that group column.
 // expression nesting bound of the binder's recursion (DuckDB's
 // max_expression_depth default): a deep left-leaning chain such as
+size_t VisibleOutputs(const BoundSelect &s) {
+  size_t n = 0;
+  for (auto &nm : s.names)
+    if (nm.rfind("__order_", 0) != 0) n++;
+  return n;
+}
+
+// a table sharded by gpu_devices anywhere under a select's sources (null: none)
+const Table *ShardedTableOf(const BoundSelect &s);
+const Table *ShardedTableOf(const BoundSource &src) {
+  switch (src.kind) {
+    case BoundSource::TABLE: return src.table && src.table->sharded() ? src.table.get() : nullptr;
+    case BoundSource::SUBQUERY: return ShardedTableOf(*src.sub);
+    case BoundSource::JOIN: {
+      const Table *t = ShardedTableOf(*src.left);
+      return t ? t : ShardedTableOf(*src.right);
+    }
+    default: return nullptr;
+  }
+}
+const Table *ShardedTableOf(const BoundSelect &s) {
+  if (const Table *t = ShardedTableOf(s.src)) return t;
+  for (auto &u : s.union_all)
+    if (const Table *t = ShardedTableOf(*u)) return t;
+  return nullptr;
+}
+
+void RefuseShardedMembership(const Table &t) {
+  ThrowError("Not implemented", "IN (subquery) over table \"" + t.name +
+                                    "\", which is sharded by gpu_devices, is not supported by the MI355X backend");
+}
+
+// x [NOT] IN (subquery): a BOOLEAN leaf over x cast to the type `=` gives x
+// and the subquery's column (the join key's rule), with the subquery's output
+// cast to the same type.  The subquery binds in a scope of its own, the
+// enclosing scopes only consulted to tell a correlated reference from an
+// unknown name.  Never folded: its value depends on the subquery's rows.
+BExprPtr BindMembership(const Expr &e, BindCtx &ctx) {
+  if (!g_bind_cat) ThrowError("Binder", "IN (subquery) is not allowed here");
+  BExprPtr x = BindExpr(*e.args[0], ctx);
+  g_outer_scopes.push_back(&ctx.scope);
+  BoundSelectPtr sub;
+  try {
+    sub = BindSelect(*e.sub, *g_bind_cat, *ctx.params);
+  } catch (...) {
+    g_outer_scopes.pop_back();
+    throw;
+  }
+  g_outer_scopes.pop_back();
+  const size_t ncols = VisibleOutputs(*sub);
+  if (ncols != 1)
+    ThrowError("Binder", "Subquery returns " + std::to_string(ncols) + " columns - expected 1");
+  if (const Table *t = ShardedTableOf(*sub)) RefuseShardedMembership(*t);
+  const LogicalType &st = sub->outputs[0]->type;
+  LogicalType t;
+  if (IsStrLit(*e.args[0]) && st.id != T_VARCHAR && st.id != T_SQLNULL) t = st;
+  else t = MaxType(x->type, st);
+  if (t.id == T_SQLNULL) t = LogicalType(T_INTEGER);
+  if (PhysOf(t) > P_U64)
+    ThrowError("Not implemented", "IN (subquery) over a key of type " + t.ToString() +
+                                      " is not supported by the MI355X backend (keys stored as integers of at most 8 bytes only)");
+  sub->outputs[0] = CastTo(sub->outputs[0], t);
+  for (auto &u : sub->union_all) u->outputs[0] = CastTo(u->outputs[0], t);
+  BExprPtr leaf = MkFunc(B_IN_SUBQUERY, LogicalType(T_BOOLEAN), {CastTo(x, t)});
+  leaf->sub = sub;
+  if (e.negated) return MkFunc(B_NOT, LogicalType(T_BOOLEAN), {leaf});
+  return leaf;
+}
+
 // 1 + 1 + ... parses iteratively but binds recursively
 static thread_local int g_bind_depth = 0;
 struct BindDepth {
@@ -1286,6 +1382,11 @@ BExprPtr BindExprInner(const Expr &e, BindCtx &ctx) {
               return BindExpr(*s, sub);
             }
         }
+        for (auto *outer : g_outer_scopes)
+          for (const ScopeCol &sc : *outer)
+            if (Lower(sc.name) == Lower(e.name) && (e.qualifier.empty() || Lower(sc.qualifier) == Lower(e.qualifier)))
+              ThrowError("Not implemented", "a correlated subquery (column \"" + e.name +
+                                                "\" belongs to the enclosing query) is not supported by the MI355X backend");
         ThrowError("Binder", "Referenced column \"" + e.name + "\" not found in FROM clause!");
       }
       return MkCol(found, ctx.scope[found].type);
@@ -1361,6 +1462,8 @@ BExprPtr BindExprInner(const Expr &e, BindCtx &ctx) {
       if (e.negated) acc = Fold(MkFunc(B_NOT, LogicalType(T_BOOLEAN), {acc}));
       return acc;
     }
+    case Expr::INSUBQ:
+      return BindMembership(e, ctx);
     case Expr::CASE: {
       std::vector<BExprPtr> ch;
       size_t i = 0;
@@ -1696,10 +1799,22 @@ static BoundSelectPtr BindSelectOne(const Select &sel, Catalog &cat, const std::
       if (o->kind == BExpr::CONST) o->type = LogicalType(T_INTEGER);
     }
   bs->names = names;
+  if (bs->src.kind == BoundSource::TABLE && bs->src.table && bs->src.table->sharded()) {
+    bool member = HasMembership(bs->where) || HasMembership(bs->having);
+    for (auto &g : bs->groups) member |= HasMembership(g);
+    for (auto &a : bs->aggs) member |= HasMembership(a.arg);
+    for (auto &o : bs->outputs) member |= HasMembership(o);
+    if (member) RefuseShardedMembership(*bs->src.table);
+  }
   return bs;
 }
 
 BoundSelectPtr BindSelect(const Select &sel, Catalog &cat, const std::vector<Value> &params) {
+  struct CatScope {  // membership subqueries of this statement bind against the same catalog
+    Catalog *prev;
+    CatScope(Catalog *c) : prev(g_bind_cat) { g_bind_cat = c; }
+    ~CatScope() { g_bind_cat = prev; }
+  } cat_scope(&cat);
   BoundSelectPtr first = BindSelectOne(sel, cat, params);
   for (auto &u : sel.union_all) {
     BoundSelectPtr b = BindSelect(*u, cat, params);
@@ -1773,6 +1888,14 @@ bool IsHostConstantSelect(const BoundSelect &s) {
   if (s.src.kind != BoundSource::ONE_ROW) return false;
   if (!s.windows.empty()) return false;  // the window stage runs on the one-row source
   if (s.where && !IsConstTree(*s.where)) return false;
+  // a membership leaf reads its subquery's rows: the device evaluates it over the one row
+  if (HasMembership(s.having)) return false;
+  for (auto &o : s.outputs)
+    if (HasMembership(o)) return false;
+  for (auto &g : s.groups)
+    if (HasMembership(g)) return false;
+  for (auto &a : s.aggs)
+    if (HasMembership(a.arg)) return false;
   for (auto &u : s.union_all)
     if (!IsHostConstantSelect(*u)) return false;
   return true;
@@ -1801,9 +1924,52 @@ static std::string ExplainSource(const BoundSource &src, int ind, const char *le
   return "";
 }
 
+// the membership leaves of a tree / of one select's own trees (not of its subqueries), each once
+static void MembershipLeaves(const BExprPtr &e, std::vector<const BExpr *> &out) {
+  if (!e) return;
+  if (e->sub && std::find(out.begin(), out.end(), e.get()) == out.end()) out.push_back(e.get());
+  for (auto &c : e->ch) MembershipLeaves(c, out);
+}
+static void SourceMembershipLeaves(const BoundSource &src, std::vector<const BExpr *> &out) {
+  if (src.kind != BoundSource::JOIN) return;
+  SourceMembershipLeaves(*src.left, out);
+  SourceMembershipLeaves(*src.right, out);
+  MembershipLeaves(src.left_key, out);
+  MembershipLeaves(src.right_key, out);
+  MembershipLeaves(src.residual, out);
+}
+static void SelectMembershipLeaves(const BoundSelect &s, std::vector<const BExpr *> &out) {
+  for (auto &o : s.outputs) MembershipLeaves(o, out);
+  SourceMembershipLeaves(s.src, out);
+  MembershipLeaves(s.where, out);
+  for (auto &g : s.groups) MembershipLeaves(g, out);
+  for (auto &a : s.aggs) MembershipLeaves(a.arg, out);
+  for (auto &w : s.windows) {
+    MembershipLeaves(w.arg, out);
+    for (auto &p : w.partition) MembershipLeaves(p, out);
+    for (auto &o : w.order) MembershipLeaves(o.expr, out);
+  }
+  MembershipLeaves(s.having, out);
+}
+
 std::string ExplainSelect(const BoundSelect &s, int ind) {
   std::string pad(ind, ' ');
   std::string out;
+  // the statement's membership leaves are numbered in the order their selects
+  // print; the outermost call owns the numbering
+  struct IdScope {
+    std::map<const BExpr *, int> ids;
+    bool owner;
+    IdScope() : owner(!g_subq_ids) {
+      if (owner) g_subq_ids = &ids;
+    }
+    ~IdScope() {
+      if (owner) g_subq_ids = nullptr;
+    }
+  } id_scope;
+  std::vector<const BExpr *> members;
+  SelectMembershipLeaves(s, members);
+  for (const BExpr *m : members) g_subq_ids->insert({m, (int)g_subq_ids->size() + 1});
   out += pad + "SELECT";
   for (size_t i = 0; i < s.outputs.size(); i++)
     out += (i ? ", " : " ") + ExprToString(*s.outputs[i]) + " AS " + s.names[i] + " :: " + s.outputs[i]->type.ToString();
@@ -1843,8 +2009,47 @@ std::string ExplainSelect(const BoundSelect &s, int ind) {
   if (s.having) out += pad + "  HAVING " + ExprToString(*s.having) + "\n";
   for (auto &o : s.order) out += pad + "  ORDER BY " + ExprToString(*o.expr) + (o.desc ? " DESC" : " ASC") + "\n";
   if (s.limit >= 0) out += pad + "  LIMIT " + std::to_string(s.limit) + " OFFSET " + std::to_string(s.offset) + "\n";
+  for (const BExpr *m : members)
+    out += pad + "  IN SUBQUERY " + std::to_string((*g_subq_ids)[m]) + " key " + m->ch[0]->type.ToString() + ": " +
+           ExprToString(*m->ch[0]) + "\n" + ExplainSelect(*m->sub, ind + 4);
   for (auto &u : s.union_all) out += pad + "UNION ALL\n" + ExplainSelect(*u, ind);
   return out;
+}
+
+// The EXPLAIN text carries every tree, constant, table and clause of a plan but
+// the rows of a VALUES source, which are compared beside it.
+static void ValuesText(const BoundSelect &s, std::string &out);
+static void ValuesText(const BExprPtr &e, std::string &out) {
+  if (!e) return;
+  if (e->sub) ValuesText(*e->sub, out);
+  for (auto &c : e->ch) ValuesText(c, out);
+}
+static void ValuesText(const BoundSource &src, std::string &out) {
+  for (auto &row : src.rows)
+    for (auto &v : row) out += (v.is_null ? std::string("NULL") : FormatValue(v)) + "\x1f";
+  if (src.sub) ValuesText(*src.sub, out);
+  if (src.kind != BoundSource::JOIN) return;
+  ValuesText(*src.left, out);
+  ValuesText(*src.right, out);
+  ValuesText(src.residual, out);
+}
+static void ValuesText(const BoundSelect &s, std::string &out) {
+  ValuesText(s.src, out);
+  ValuesText(s.where, out);
+  ValuesText(s.having, out);
+  for (auto &o : s.outputs) ValuesText(o, out);
+  for (auto &g : s.groups) ValuesText(g, out);
+  for (auto &a : s.aggs) ValuesText(a.arg, out);
+  for (auto &u : s.union_all) ValuesText(*u, out);
+}
+
+bool BoundSelectEq(const BoundSelect &a, const BoundSelect &b) {
+  if (&a == &b) return true;
+  if (ExplainSelect(a) != ExplainSelect(b)) return false;
+  std::string va, vb;
+  ValuesText(a, va);
+  ValuesText(b, vb);
+  return va == vb;
 }
 
 TablePtr Catalog::Find(const std::string &name) const {
@@ -1856,12 +2061,13 @@ TablePtr Catalog::Find(const std::string &name) const {
 
 namespace mbx {
 
+static void CollectPlanNodes(const BoundSelect &s, std::set<const BExpr *> &out);
 static void CollectExprNodes(const BExpr *e, std::set<const BExpr *> &out) {
   if (!e || !out.insert(e).second) return;
   for (auto &c : e->ch) CollectExprNodes(c.get(), out);
+  if (e->sub) CollectPlanNodes(*e->sub, out);  // a membership subquery's parameters live in the same plan
 }
 
-static void CollectPlanNodes(const BoundSelect &s, std::set<const BExpr *> &out);
 static void CollectSourceNodes(const BoundSource &src, std::set<const BExpr *> &out) {
   if (src.sub) CollectPlanNodes(*src.sub, out);
   if (src.kind != BoundSource::JOIN) return;

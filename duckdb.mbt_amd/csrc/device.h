@@ -321,6 +321,11 @@ void JoinBuild(const int64_t *sorted_keys, int64_t n, JoinEntry *tab, int64_t ca
 // counts[i] = build rows that match probe row i (0 for a NULL key), starts[i] = their run's start
 void JoinProbeCount(const void *col, int phys, const uint64_t *valid, int64_t n, const JoinEntry *tab, int64_t cap,
                     int64_t *counts, int32_t *starts, int32_t *err, hipStream_t s);
+// x IN (subquery) (join_mark_plan.h): mark[i] = the BOOLEAN byte of probe row i against the set whose
+// non-NULL keys are in tab (null / cap 0: none), mark_valid (optional, Words64(n) words, each written
+// whole) its validity; set_has_null: a miss is NULL.  The constant-FALSE case never gets here.
+void JoinProbeMark(const void *col, int phys, const uint64_t *valid, int64_t n, const JoinEntry *tab, int64_t cap,
+                   bool set_has_null, uint8_t *mark, uint64_t *mark_valid, int32_t *err, hipStream_t s);
 // offsets: ScanLengths of counts (n + 1 entries, offsets[n] == total); build_rows: the build row
 // numbers in sorted-key order.  Writes the total pairs, probe-row-major, build rows ascending.
 void JoinExpand(const int64_t *offsets, const int32_t *starts, int64_t n, int64_t total, const int64_t *build_rows,

@@ -94,6 +94,8 @@ struct DevicePool {
   ~DevicePool() { ReleaseAll(); }
 };
 
+struct DevBuf;
+
 struct Engine {
   int device = 0;
   std::shared_ptr<DevicePool> pool;
@@ -197,6 +199,17 @@ struct Engine {
     const char *last_reason = "";
   } hist_host;
   int64_t scan_codes_min_rows = 0, scan_codes_bits_min_rows = 0, scan_codes_planes_min_rows = 0;
+  // IN (subquery): the sets of the running statement, each subquery run and
+  // its table built once however often its leaf is lowered (MarkSetScope)
+  struct MarkSet {
+    std::shared_ptr<const BoundSelect> sub;
+    int64_t rows = 0, nulls = 0;  // of the subquery; of them NULL keys
+    std::shared_ptr<struct DevBuf> tab;  // null: no non-NULL key
+    int64_t cap = 0;
+  };
+  std::vector<MarkSet> mark_sets;
+  int mark_depth = 0;
+  Connection *mark_conn = nullptr;  // the connection the subqueries run on
   bool profile = false;
   std::vector<ProfEvent> events;
   // kernels timed on shard engines during this query (gpu_devices)
@@ -286,6 +299,21 @@ struct ProfScope {
   }
 };
 
+// Around a statement's run: the membership sets made inside are dropped when
+// the outermost scope ends, however it ends.
+struct MarkSetScope {
+  Engine &e;
+  Connection *prev;
+  MarkSetScope(Engine &en, Connection &c) : e(en), prev(en.mark_conn) {
+    if (e.mark_depth++ == 0) e.mark_sets.clear();
+    e.mark_conn = &c;
+  }
+  ~MarkSetScope() {
+    e.mark_conn = prev;
+    if (--e.mark_depth == 0) e.mark_sets.clear();
+  }
+};
+
 // ---------------------------------------------------------------------------
 // device buffers and relations
 // ---------------------------------------------------------------------------
@@ -365,10 +393,11 @@ void UploadHostColumn(Engine &e, const HostColumn &hc, int64_t n, DCol &d);
 DRel UploadRows(Engine &e, const std::vector<std::vector<Value>> &rows, const std::vector<LogicalType> &types);
 DCol AllocOut(Engine &e, const LogicalType &t, int64_t n, bool with_valid, bool zero_valid = true);
 DRel FilterProject(Engine &e, const DRel &rel, const BExprPtr &pred, const std::vector<BExprPtr> &exprs);
-// Evaluates every VARCHAR predicate leaf of `trees` (entries may be null) with
-// the str_match kernels into BOOLEAN columns appended to a copy of rel
-// (`lowered`) and rewrites the trees, copy on write, to read those columns.
-// false: no tree has such a leaf; trees and lowered are untouched.
+// Evaluates every leaf of `trees` (entries may be null) that the VM cannot
+// compute -- a VARCHAR predicate, with the str_match kernels; x IN (subquery),
+// with the mark join (join_probe_mark) -- into BOOLEAN columns appended to a
+// copy of rel (`lowered`) and rewrites the trees, copy on write, to read those
+// columns.  false: no tree has such a leaf; trees and lowered are untouched.
 bool LowerStringPredicates(Engine &e, const DRel &rel, std::vector<BExprPtr> &trees, DRel &lowered);
 const BExpr *StripWidening(const BExpr *x);
 bool RangePredicate(const BExpr &p, int *col, i128 *lo, i128 *hi);
@@ -414,6 +443,18 @@ struct JoinPrepared {
   DevBufPtr max_run;      // with want_max_run: a device word, the longest run of equal build keys
 };
 JoinPrepared JoinPrepare(Engine &e, Connection &c, const BoundSource &src, bool want_max_run = false);
+// a key expression over r as a column: a bare column read in place, anything else evaluated
+DCol KeyColumn(Engine &e, const DRel &r, const BExprPtr &k);
+// The build half, shared by the join and by IN (subquery): the n keys of an
+// integer column, NULLs filtered out, as sorted row numbers and the table of
+// the distinct keys (join_keys, radix_sort, join_build).  nb == 0 (no non-NULL
+// key): no buffers.
+struct JoinTable {
+  DevBufPtr rows2, tab, max_run;
+  int64_t nb = 0, cap = 0;  // non-NULL keys; table slots
+  int64_t nulls = 0;        // keys that were NULL
+};
+JoinTable JoinBuildTable(Engine &e, DCol bkey, int64_t n, bool want_max_run = false);
 // the rest: counts, offsets, the limit, the row numbers of the pairs, the gathers, the residual
 DRel JoinPairs(Engine &e, Connection &c, const BoundSource &src, const JoinPrepared &j);
 DRel JoinRel(Engine &e, Connection &c, const BoundSource &src);  // JoinPairs(JoinPrepare(...))

@@ -25,6 +25,8 @@
 
 #include "exec.h"
 #include "jit.h"
+#include "join_mark_plan.h"
+#include "join_plan.h"
 #include "hostlink.h"
 #include "vm_compile.h"
 #include "knobs.h"
@@ -329,7 +331,52 @@ static void MaterializeStrings(Engine &e, DCol &out, const DCol *src, const StrP
 // tree is rebuilt with a reference to that column in the leaf's place.  The
 // bound plan itself is never changed: a prepared statement patches new
 // constants into its nodes, and the next execute must read them here.
+//
+// x IN (subquery) is the same kind of leaf.  The subquery runs once per
+// statement and its non-NULL keys go into the join's table (MarkSetOf); the
+// left operand becomes a key column the way a join key does, and
+// join_probe_mark writes the mark's byte and, where join_mark_plan.h asks for
+// one, its validity.  NOT IN is the VM's NOT over that column.
 namespace {
+
+// the same tree: kinds, types, columns, constants, and the subqueries of membership leaves
+bool SameTree(const BExpr &a, const BExpr &b) {
+  if (a.kind != b.kind || a.type != b.type) return false;
+  if (a.kind == BExpr::COL) return a.col == b.col;
+  if (a.kind == BExpr::CONST)
+    return a.cval.is_null == b.cval.is_null && (a.cval.is_null || FormatValue(a.cval) == FormatValue(b.cval));
+  if (a.op != b.op || a.ch.size() != b.ch.size() || (bool)a.sub != (bool)b.sub) return false;
+  for (size_t i = 0; i < a.ch.size(); i++)
+    if (!SameTree(*a.ch[i], *b.ch[i])) return false;
+  return !a.sub || a.sub == b.sub || BoundSelectEq(*a.sub, *b.sub);
+}
+
+// The set of a membership subquery in the running statement: the subquery is
+// run and its table built the first time any leaf asks, whichever lowering
+// that is in.  (By value: a nested subquery's set may be added meanwhile.)
+Engine::MarkSet MarkSetOf(Engine &e, const std::shared_ptr<BoundSelect> &sub) {
+  if (!e.mark_conn) ThrowError("Internal", "an IN (subquery) leaf outside a statement's run");
+  for (auto &m : e.mark_sets)
+    if (m.sub == sub) return m;
+  for (auto &m : e.mark_sets)
+    if (BoundSelectEq(*m.sub, *sub)) return m;
+  Engine::MarkSet m;
+  m.sub = sub;
+  DRel r = RunSelectDev(e, *e.mark_conn, *sub);
+  m.rows = r.n;
+  if (r.n > 0) {
+    auto k = std::make_shared<BExpr>();
+    k->kind = BExpr::COL;
+    k->col = 0;
+    k->type = r.cols[0].type;
+    const JoinTable t = JoinBuildTable(e, KeyColumn(e, r, k), r.n);
+    m.nulls = t.nulls;
+    m.tab = t.tab;
+    m.cap = t.tab ? t.cap : 0;
+  }
+  e.mark_sets.push_back(m);
+  return m;
+}
 
 bool IsStrColumn(const DRel &rel, const BExpr &x) {
   return x.kind == BExpr::COL && x.col >= 0 && x.col < (int)rel.cols.size() && !(rel.range && x.col == 0) &&
@@ -478,11 +525,46 @@ struct StrLowering {
     return Append(d);
   }
 
+  // x IN (subquery): the mark column (join_mark_plan.h)
+  BExprPtr MarkLeaf(const BExpr &x) {
+    const Engine::MarkSet set = MarkSetOf(e, x.sub);
+    JoinMarkFacts f;
+    f.set_rows = set.rows;
+    f.set_nulls = set.nulls;
+    if (JoinMarkDecide(f).constant_false) {  // FALSE for every row, a NULL key included: nothing to launch
+      const JoinMarkCellValue c = JoinMarkCell(false, false, true, false);
+      return BoolConst(c.value != 0, !c.valid);
+    }
+    const DCol key = KeyColumn(e, rel, x.ch[0]);
+    if (key.phys > P_U64) ThrowError("Internal", "IN (subquery) key is not stored as an integer");
+    f.probe_nullable = key.validity != nullptr;
+    const JoinMarkPlan plan = JoinMarkDecide(f);
+    DCol d = NewBool(nullptr);
+    if (plan.validity) {
+      auto v = Alloc(e, Words64(std::max<int64_t>(rel.n, 1)) * 8);
+      d.validity = (uint64_t *)v->p;
+      d.owners.push_back(v);
+    }
+    // per row: the key, one 16-B entry, the mark's byte and its validity bit
+    ProfScope ps(e, "join_probe_mark",
+                 (double)rel.n * (PhysSize(key.phys) + sizeof(JoinEntry) + 1 + (plan.validity ? 1.0 / 8 : 0)), rel.n);
+    dev::JoinProbeMark(key.data, key.phys, key.validity, rel.n, plan.lookup ? (const JoinEntry *)set.tab->p : nullptr,
+                       plan.lookup ? set.cap : 0, plan.set_has_null, (uint8_t *)d.data, d.validity, e.d_err, e.stream);
+    return Append(d);
+  }
+
   BExprPtr Rewrite(const BExprPtr &x) {
     if (!x || x->kind != BExpr::FUNC) return x;
+    if (x->op == B_IN_SUBQUERY && x->sub) {
+      for (auto &p : done)
+        if (p.first->op == B_IN_SUBQUERY && SameTree(*p.first, *x)) return p.second;
+      BExprPtr r = MarkLeaf(*x);
+      done.push_back({x, r});
+      return r;
+    }
     if (IsStrLeaf(rel, *x)) {
       for (auto &p : done)
-        if (SameStrLeaf(*p.first, *x)) return p.second;
+        if (p.first->op != B_IN_SUBQUERY && SameStrLeaf(*p.first, *x)) return p.second;
       BExprPtr r = Leaf(*x);
       done.push_back({x, r});
       return r;
@@ -1911,6 +1993,7 @@ ResultPtr ExecuteSelect(Connection &c, const BoundSelect &s) {
     DeferScope(Engine &en, const BoundSelect &s) : e(en) { e.defer_count_for = &s; }
     ~DeferScope() { e.defer_count_for = nullptr; }
   } defer(e, s);
+  MarkSetScope marks(e, c);
   DRel r = RunSelectDev(e, c, s, true);
   std::vector<std::string> names(s.names.begin(), s.names.begin() + VisibleCols(s));
   ResultPtr res = ToHost(e, r, names, 0, -1, names.size(), true);  // raises pending device errors
@@ -1933,6 +2016,7 @@ DeviceResultPtr ExecuteSelectDevice(Connection &c, const BoundSelect &s, StreamS
   BeginProfile(c, e);
   e.tail_serial++;
   auto d = std::make_shared<DeviceResult>();
+  MarkSetScope marks(e, c);
   d->r = RunSelectDev(e, c, s, true);
   d->names.assign(s.names.begin(), s.names.begin() + VisibleCols(s));
   CheckError(e);  // (its copy of the error word waits for the whole stream)

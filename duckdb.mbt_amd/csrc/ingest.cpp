@@ -364,6 +364,7 @@ void ExecuteInsertSelect(Connection &c, Table &t, const BoundSelect &s, const st
       ~Want() { e.want_zone_maps = false; }
     } want{e};
     e.want_zone_maps = true;
+    MarkSetScope marks(e, c);
     r = RunSelectDev(e, c, s);
   }
   AppendCast(e, t, r, col_map);

@@ -13,7 +13,8 @@
 // the columns of each side.  The ON clause's other conjuncts (the residual)
 // filter the joined relation.  The kernels are join_kernels.hip.
 //
-// JoinPrepare runs a join up to its table, JoinPairs does the rest.  An
+// JoinBuildTable is the build half on its own (x IN (subquery) builds its set
+// with it, executor.cpp).  JoinPrepare runs a join up to its table, JoinPairs does the rest.  An
 // aggregate without GROUP BY over a join (JoinAggregate) prepares the join and,
 // where join_agg_plan.h takes the statement, never makes the pairs: one kernel
 // probes and interprets the residual, the WHERE and the aggregate arguments per
@@ -42,12 +43,6 @@ std::vector<BExprPtr> AllCols(const DRel &r) {
   return out;
 }
 
-// a key that is a bare column is read in place; anything else is evaluated
-DCol KeyColumn(Engine &e, const DRel &r, const BExprPtr &k) {
-  if (k->kind == BExpr::COL && !(r.range && k->col == 0)) return r.cols[k->col];
-  return FilterProject(e, r, nullptr, {k}).cols[0];
-}
-
 // no row of either side: the columns of both, empty
 DRel EmptyJoin(Engine &e, const DRel &l, const DRel &r) {
   auto none = Alloc(e, 16);
@@ -58,6 +53,68 @@ DRel EmptyJoin(Engine &e, const DRel &l, const DRel &r) {
 }
 
 }  // namespace
+
+// a key that is a bare column is read in place; anything else is evaluated
+DCol KeyColumn(Engine &e, const DRel &r, const BExprPtr &k) {
+  if (k->kind == BExpr::COL && !(r.range && k->col == 0)) return r.cols[k->col];
+  return FilterProject(e, r, nullptr, {k}).cols[0];
+}
+
+// The build half of a join: `bkey`'s n keys as int64 beside their row numbers
+// (NULL keys leave first), sorted, and every distinct key in the table.
+JoinTable JoinBuildTable(Engine &e, DCol bkey, int64_t n, bool want_max_run) {
+  JoinTable t;
+  if (n > kJoinMaxBuildRows)
+    ThrowError("Out of Range", "join input of " + std::to_string(n) + " rows, more than the 2147483647 a join side may have");
+  if (bkey.phys > P_U64) ThrowError("Internal", "join key is not stored as an integer");
+  int64_t nb = n;
+  if (nb == 0) return t;
+  auto keys = Alloc(e, nb * 8), keys2 = Alloc(e, nb * 8);
+  t.rows2 = Alloc(e, nb * 8);
+  DevBufPtr rows_buf;
+  int64_t *rows = nullptr;
+  DRel kept;  // owns the filtered key and row columns
+  if (bkey.validity) {
+    DRel kr;
+    kr.n = nb;
+    kr.cols.push_back(bkey);
+    DCol rc = AllocOut(e, LogicalType(T_BIGINT), nb, false);
+    dev::Iota((int64_t *)rc.data, nb, 0, e.stream);
+    kr.cols.push_back(rc);
+    auto notnull = std::make_shared<BExpr>();
+    notnull->kind = BExpr::FUNC;
+    notnull->op = B_ISNOTNULL;
+    notnull->type = LogicalType(T_BOOLEAN);
+    notnull->ch.push_back(ColRef(0, bkey.type));
+    kept = FilterProject(e, kr, notnull, AllCols(kr));
+    nb = kept.n;
+    t.nulls = n - nb;
+    if (nb == 0) return t;
+    bkey = kept.cols[0];
+    rows = (int64_t *)kept.cols[1].data;
+    ProfScope ps(e, "join_keys", (double)nb * (PhysSize(bkey.phys) + 8), nb);
+    dev::JoinKeys(bkey.data, bkey.phys, nb, (int64_t *)keys->p, nullptr, e.stream);
+  } else {
+    rows_buf = Alloc(e, nb * 8);
+    rows = (int64_t *)rows_buf->p;
+    ProfScope ps(e, "join_keys", (double)nb * (PhysSize(bkey.phys) + 16), nb);
+    dev::JoinKeys(bkey.data, bkey.phys, nb, (int64_t *)keys->p, rows, e.stream);
+  }
+  {
+    ProfScope ps(e, "radix_sort", (double)nb * 16 * 2, nb);
+    dev::SortPairs((uint64_t *)keys->p, rows, (uint64_t *)keys2->p, (int64_t *)t.rows2->p, nb, e.stream);
+  }
+  t.nb = nb;
+  t.cap = JoinCapacity(nb);
+  t.tab = Alloc(e, (size_t)t.cap * sizeof(JoinEntry), true);
+  if (want_max_run) t.max_run = Alloc(e, sizeof(uint32_t), true);
+  {
+    ProfScope ps(e, "join_build", (double)nb * 8 + (double)t.cap * sizeof(JoinEntry), nb);
+    dev::JoinBuild((const int64_t *)keys2->p, nb, (JoinEntry *)t.tab->p, t.cap, e.d_err, e.stream,
+                   t.max_run ? (uint32_t *)t.max_run->p : nullptr);
+  }
+  return t;
+}
 
 JoinPrepared JoinPrepare(Engine &e, Connection &c, const BoundSource &src, bool want_max_run) {
   JoinPrepared j;
@@ -82,54 +139,13 @@ JoinPrepared JoinPrepare(Engine &e, Connection &c, const BoundSource &src, bool 
   j.pkey = KeyColumn(e, probe, j.p == 0 ? src.left_key : src.right_key);
   if (bkey.phys > P_U64 || j.pkey.phys > P_U64) ThrowError("Internal", "join key is not stored as an integer");
 
-  // build keys as int64 beside their row numbers; NULL keys leave first
-  int64_t nb = build.n;
-  auto keys = Alloc(e, nb * 8), keys2 = Alloc(e, nb * 8);
-  j.rows2 = Alloc(e, nb * 8);
-  DevBufPtr rows_buf;
-  int64_t *rows = nullptr;
-  DRel kept;  // owns the filtered key and row columns
-  if (bkey.validity) {
-    DRel kr;
-    kr.n = nb;
-    kr.cols.push_back(bkey);
-    DCol rc = AllocOut(e, LogicalType(T_BIGINT), nb, false);
-    dev::Iota((int64_t *)rc.data, nb, 0, e.stream);
-    kr.cols.push_back(rc);
-    auto notnull = std::make_shared<BExpr>();
-    notnull->kind = BExpr::FUNC;
-    notnull->op = B_ISNOTNULL;
-    notnull->type = LogicalType(T_BOOLEAN);
-    notnull->ch.push_back(ColRef(0, bkey.type));
-    kept = FilterProject(e, kr, notnull, AllCols(kr));
-    nb = kept.n;
-    if (nb == 0) {
-      j.empty = true;
-      return j;
-    }
-    bkey = kept.cols[0];
-    rows = (int64_t *)kept.cols[1].data;
-    ProfScope ps(e, "join_keys", (double)nb * (PhysSize(bkey.phys) + 8), nb);
-    dev::JoinKeys(bkey.data, bkey.phys, nb, (int64_t *)keys->p, nullptr, e.stream);
-  } else {
-    rows_buf = Alloc(e, nb * 8);
-    rows = (int64_t *)rows_buf->p;
-    ProfScope ps(e, "join_keys", (double)nb * (PhysSize(bkey.phys) + 16), nb);
-    dev::JoinKeys(bkey.data, bkey.phys, nb, (int64_t *)keys->p, rows, e.stream);
+  const JoinTable t = JoinBuildTable(e, bkey, build.n, want_max_run);
+  if (t.nb == 0) {  // every build key was NULL
+    j.empty = true;
+    return j;
   }
-  {
-    ProfScope ps(e, "radix_sort", (double)nb * 16 * 2, nb);
-    dev::SortPairs((uint64_t *)keys->p, rows, (uint64_t *)keys2->p, (int64_t *)j.rows2->p, nb, e.stream);
-  }
-  j.nb = nb;
-  j.cap = JoinCapacity(nb);
-  j.tab = Alloc(e, (size_t)j.cap * sizeof(JoinEntry), true);
-  if (want_max_run) j.max_run = Alloc(e, sizeof(uint32_t), true);
-  {
-    ProfScope ps(e, "join_build", (double)nb * 8 + (double)j.cap * sizeof(JoinEntry), nb);
-    dev::JoinBuild((const int64_t *)keys2->p, nb, (JoinEntry *)j.tab->p, j.cap, e.d_err, e.stream,
-                   j.max_run ? (uint32_t *)j.max_run->p : nullptr);
-  }
+  j.rows2 = t.rows2, j.tab = t.tab, j.max_run = t.max_run;
+  j.nb = t.nb, j.cap = t.cap;
   return j;
 }
 
@@ -258,7 +274,9 @@ DRel JoinAggregate(Engine &e, Connection &c, const BoundSelect &s) {
   f.max_aggs = VM_MAX_OUT;
   f.max_run_limit = c.opts.join_agg_max_run;
   f.varchar = HasVarchar(src.residual) || HasVarchar(s.where);
+  f.membership = HasMembership(src.residual) || HasMembership(s.where);
   for (auto &a : s.aggs) {
+    f.membership |= HasMembership(a.arg);
     f.distinct |= a.distinct;
     f.varchar |= HasVarchar(a.arg);
     f.minmax_128 |= a.arg && (a.kind == A_MIN || a.kind == A_MAX) && ClassOf(a.arg->type) == VC_I128;

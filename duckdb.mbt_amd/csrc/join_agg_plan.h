@@ -28,6 +28,7 @@ struct JoinAggFacts {
   bool distinct = false;        // a DISTINCT aggregate
   bool varchar = false;         // a VARCHAR column, argument or predicate in the residual, the WHERE or an argument
   bool minmax_128 = false;      // MIN / MAX of a 128-bit value
+  bool membership = false;      // an IN (subquery) leaf in the residual, the WHERE or an argument
   int n_aggs = 0;
   int max_aggs = 0;             // VM_MAX_OUT
   bool compile_failed = false;  // VmCompiler refused one of the three stages
@@ -45,6 +46,7 @@ inline JoinAggChoice JoinAggDecide(const JoinAggFacts &f) {
   if (f.distinct) return {false, "a DISTINCT aggregate"};
   if (f.varchar) return {false, "a VARCHAR column, argument or predicate"};
   if (f.minmax_128) return {false, "MIN/MAX of a 128-bit value"};
+  if (f.membership) return {false, "an IN (subquery) leaf, which is lowered to a column first"};
   if (f.n_aggs > f.max_aggs) return {false, "more aggregates than the program has outputs"};
   if (f.compile_failed) return {false, "the expression compiler refused a stage"};
   if (f.max_run > f.max_run_limit) return {false, "a build run longer than mbx_join_agg_max_run"};

@@ -7,6 +7,9 @@
 //                     open-addressing table of join_plan.h (one CAS per key)
 //   join_probe_count  per probe row: hash, walk, write the match count (int64)
 //                     and the run start (int32); no atomics on this side
+//   join_probe_mark   x IN (subquery): per probe row the lookup, then the mark's
+//                     byte and, where the plan asks for one, its validity bit
+//                     (join_mark_plan.h); one wave64 ballot is one validity word
 //   join_expand       per OUTPUT row j in [0, total): the probe row whose
 //                     [offsets[p], offsets[p + 1]) holds j and the build row at
 //                     that place of its run
@@ -33,6 +36,7 @@
 
 #include "device.h"
 #include "join_agg_plan.h"
+#include "join_mark_plan.h"
 #include "join_plan.h"
 #include "phys.h"
 #include "types.h"
@@ -168,6 +172,73 @@ __global__ __launch_bounds__(kJoinBlock) void join_probe_count_kernel(const T *_
     store_pair(counts, i0, both, cnt[0], cnt[1]);
     starts[i0] = st[0];
     if (both) starts[i0 + 1] = st[1];
+  }
+}
+
+// x IN (subquery).  A wave owns kMarkGroups x 64 consecutive rows at a time:
+// lane t takes rows base + 64 g + t, so a group's keys are one contiguous
+// wave-wide load, its marks one contiguous run of bytes, and its validity bits
+// exactly one word, which the ballot assembles and lane 0 stores whole (base
+// is a multiple of 64 x kMarkGroups).  The first entry of every group's probe
+// sequence is loaded before any is looked at: kMarkGroups independent 16-B
+// table reads per lane are in flight.  A key whose first slot holds another
+// key walks on with JoinLookup.  Rows at or past n vote 0, which leaves the
+// last word's unused bits clear like every other validity writer's; a word
+// wholly past n is not written.  tab may be null with cap == 0 (a set of
+// NULLs only): nothing is found.
+constexpr int kMarkGroups = 4;
+constexpr int kMarkBlocksPerCU = 4;
+constexpr int kMarkWaveRows = 64 * kMarkGroups;
+
+template <typename T>
+__global__ __launch_bounds__(kJoinBlock) void join_probe_mark_kernel(const T *__restrict__ col,
+                                                                     const uint64_t *__restrict__ valid, const int64_t n,
+                                                                     const JoinEntry *__restrict__ tab, const int64_t cap,
+                                                                     const bool set_has_null, uint8_t *__restrict__ mark,
+                                                                     uint64_t *__restrict__ mark_valid,
+                                                                     int32_t *__restrict__ err) {
+  const int lane = threadIdx.x & 63;
+  const int64_t wave = (int64_t)blockIdx.x * (kJoinBlock / 64) + (threadIdx.x >> 6);
+  const int64_t nwaves = (int64_t)gridDim.x * (kJoinBlock / 64);
+  const int64_t nchunks = (n + kMarkWaveRows - 1) / kMarkWaveRows;
+  for (int64_t chunk = wave; chunk < nchunks; chunk += nwaves) {
+    const int64_t base = chunk * kMarkWaveRows;
+    int64_t k[kMarkGroups];
+    bool live[kMarkGroups], kv[kMarkGroups];
+    JoinEntry first[kMarkGroups];
+#pragma unroll
+    for (int g = 0; g < kMarkGroups; g++) {
+      const int64_t row = base + 64 * g + lane;
+      live[g] = row < n;
+      k[g] = live[g] ? (int64_t)col[row] : 0;
+      kv[g] = live[g] && row_valid(valid, row);
+    }
+#pragma unroll
+    for (int g = 0; g < kMarkGroups; g++) {
+      first[g].len = 0;
+      if (kv[g] && cap > 0) first[g] = tab[JoinSlot(JoinHash(k[g]), 0, cap)];
+    }
+#pragma unroll
+    for (int g = 0; g < kMarkGroups; g++) {
+      if (base + 64 * g >= n) break;  // (the whole wave leaves together)
+      bool found = false;
+      if (first[g].len != 0) {
+        found = first[g].key == k[g];
+        if (!found) {
+          JoinEntry e;
+          const int64_t s = JoinLookup(tab, cap, k[g], &e);
+          found = s >= 0;
+          if (s == kJoinTableFull) atomicCAS(err, 0, (int32_t)E_JOIN_FULL);
+        }
+      }
+      const JoinMarkCellValue c = JoinMarkCell(found, kv[g], false, set_has_null);
+      const int64_t row = base + 64 * g + lane;
+      if (live[g]) mark[row] = c.value;
+      if (mark_valid) {
+        const uint64_t word = __ballot(live[g] && c.valid);
+        if (lane == 0) mark_valid[(base >> 6) + g] = word;
+      }
+    }
   }
 }
 
@@ -428,6 +499,16 @@ void launch_probe(const void *col, const uint64_t *valid, int64_t n, const JoinE
                      tab, cap, counts, starts, err);
 }
 
+template <typename T>
+void launch_mark(const void *col, const uint64_t *valid, int64_t n, const JoinEntry *tab, int64_t cap, bool set_has_null,
+                 uint8_t *mark, uint64_t *mark_valid, int32_t *err, hipStream_t s) {
+  const int64_t nchunks = (n + kMarkWaveRows - 1) / kMarkWaveRows;
+  const int64_t want = (nchunks + kJoinBlock / 64 - 1) / (kJoinBlock / 64);
+  const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(want, (int64_t)NumCUs() * kMarkBlocksPerCU));
+  hipLaunchKernelGGL((join_probe_mark_kernel<T>), dim3(grid), dim3(kJoinBlock), 0, s, (const T *)col, valid, n, tab, cap,
+                     set_has_null, mark, mark_valid, err);
+}
+
 void CheckLaunch(const char *what) {
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) throw std::runtime_error(std::string(what) + ": " + hipGetErrorString(e));
@@ -474,6 +555,24 @@ void JoinProbeCount(const void *col, int phys, const uint64_t *valid, int64_t n,
     default: throw std::runtime_error("join_probe_count: not an integer column");
   }
   CheckLaunch("join_probe_count");
+}
+
+void JoinProbeMark(const void *col, int phys, const uint64_t *valid, int64_t n, const JoinEntry *tab, int64_t cap,
+                   bool set_has_null, uint8_t *mark, uint64_t *mark_valid, int32_t *err, hipStream_t s) {
+  if (n <= 0) return;
+  if (!tab) cap = 0;
+  switch (phys) {
+    case P_U8: launch_mark<uint8_t>(col, valid, n, tab, cap, set_has_null, mark, mark_valid, err, s); break;
+    case P_I8: launch_mark<int8_t>(col, valid, n, tab, cap, set_has_null, mark, mark_valid, err, s); break;
+    case P_I16: launch_mark<int16_t>(col, valid, n, tab, cap, set_has_null, mark, mark_valid, err, s); break;
+    case P_U16: launch_mark<uint16_t>(col, valid, n, tab, cap, set_has_null, mark, mark_valid, err, s); break;
+    case P_I32: launch_mark<int32_t>(col, valid, n, tab, cap, set_has_null, mark, mark_valid, err, s); break;
+    case P_U32: launch_mark<uint32_t>(col, valid, n, tab, cap, set_has_null, mark, mark_valid, err, s); break;
+    case P_I64: launch_mark<int64_t>(col, valid, n, tab, cap, set_has_null, mark, mark_valid, err, s); break;
+    case P_U64: launch_mark<uint64_t>(col, valid, n, tab, cap, set_has_null, mark, mark_valid, err, s); break;
+    default: throw std::runtime_error("join_probe_mark: not an integer column");
+  }
+  CheckLaunch("join_probe_mark");
 }
 
 void JoinExpand(const int64_t *offsets, const int32_t *starts, int64_t n, int64_t total, const int64_t *build_rows,

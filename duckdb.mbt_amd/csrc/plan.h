@@ -19,6 +19,9 @@ enum BOp : uint8_t {
   B_CAST, B_CASE, B_COALESCE, B_CONCAT, B_SYNTH, B_LENGTH, B_LOWER, B_UPPER,
   // VARCHAR matches against a constant: ch = [string, pattern (, escape)] / [string, constant]
   B_LIKE, B_PREFIX, B_SUFFIX, B_CONTAINS,
+  // x IN (subquery): ch = [x cast to the key type], BExpr::sub the one-column
+  // subquery whose output is cast to the same type; three-valued (join_mark_plan.h)
+  B_IN_SUBQUERY,
 };
 
 enum AggKind : uint8_t { A_COUNT_STAR, A_COUNT, A_SUM, A_MIN, A_MAX, A_AVG };
@@ -34,6 +37,7 @@ struct BExpr {
   BOp op = B_ADD;
   std::vector<BExprPtr> ch;
   // CASE: ch = [when0, then0, when1, then1, ..., else]
+  std::shared_ptr<struct BoundSelect> sub;  // B_IN_SUBQUERY: the uncorrelated subquery
 };
 
 struct AggSpec {
@@ -124,7 +128,12 @@ BoundSelectPtr BindSelectCapture(const Select &sel, Catalog &cat, const std::vec
 Value EvalConst(const BExpr &e);
 Value CastValue(const Value &v, const LogicalType &to, bool try_cast = false);
 LogicalType MaxType(const LogicalType &a, const LogicalType &b);  // implicit common super type
-bool IsConstTree(const BExpr &e);
+bool IsConstTree(const BExpr &e);  // (false for a tree with a membership leaf: it reads the subquery's rows)
+// a B_IN_SUBQUERY leaf anywhere in the tree (null: none)
+bool HasMembership(const BExprPtr &e);
+// the same plan: every tree, source and constant (two separately bound copies
+// of one subquery text are equal)
+bool BoundSelectEq(const BoundSelect &a, const BoundSelect &b);
 // The matcher plan (str_match.h) of a B_LIKE / B_PREFIX / B_SUFFIX / B_CONTAINS
 // node whose pattern (and escape) are non-NULL constants; raises LIKE's
 // pattern errors.  The binder's folder and the executor's lowering both plan

@@ -629,9 +629,18 @@ class Parser {
         continue;
       }
       if (AcceptKw("in")) {
+        ExpectOp("(");
+        if (IsKw("select")) {  // membership in a subquery: any select a FROM-subquery may hold
+          auto q = Mk(Expr::INSUBQ);
+          q->negated = neg;
+          q->args.push_back(l);
+          q->sub = ParseSelectUnion();
+          ExpectOp(")");
+          l = q;
+          continue;
+        }
         auto e = Mk(Expr::INLIST);
         e->negated = neg;
-        ExpectOp("(");
         e->args.push_back(l);
         do e->args.push_back(ParseExpr());
         while (AcceptOp(","));

@@ -5,6 +5,7 @@
 // This parser covers the statements the reference's tests and the benchmark
 // configurations issue: SELECT [DISTINCT] ... FROM {table | range(..) [tbl(col)]
 // | (VALUES ..) t(cols) | (subquery)} {[INNER] JOIN <the same> ON cond}* [WHERE]
+// (with x [NOT] IN (subquery) wherever an expression may stand)
 // [GROUP BY] [HAVING] [ORDER BY] [LIMIT/OFFSET] [UNION ALL ...], window calls f(..) OVER (..)
 // in the select list, CREATE TABLE [AS SELECT], INSERT INTO ...
 // VALUES/SELECT, DROP TABLE.
@@ -45,6 +46,7 @@ struct Expr {
     BETWEEN,   // args[0] [NOT] BETWEEN args[1] AND args[2]
     INLIST,    // args[0] [NOT] IN (args[1..])
     LIKE,      // args[0] [NOT] LIKE args[1] [ESCAPE args[2]]
+    INSUBQ,    // args[0] [NOT] IN (sub): membership in a one-column subquery
   };
   Kind kind = CONST;
   Value val;
@@ -60,6 +62,7 @@ struct Expr {
   std::string alias;
   std::string text;          // original text for column naming
   std::shared_ptr<OverClause> over;  // FUNC: f(args) OVER (...), a window call
+  SelectPtr sub;             // INSUBQ: the subquery
 };
 
 struct TableRef {

@@ -332,6 +332,9 @@ struct VmCompiler {
         // over a VARCHAR column these never get here (LowerStringPredicates)
         ThrowError("Not implemented", "a VARCHAR match over anything but a VARCHAR column of the scanned relation is not "
                                       "supported on the MI355X device path: " + ExprToString(e));
+      case B_IN_SUBQUERY:
+        // lowered to a BOOLEAN column before any program is compiled (LowerStringPredicates)
+        ThrowError("Internal", "an IN (subquery) leaf reached the expression compiler: " + ExprToString(e));
       default:
         ThrowError("Not implemented", "function " + ExprToString(e) + " is not supported on the MI355X device path");
     }
