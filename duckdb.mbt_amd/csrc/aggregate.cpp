@@ -8,6 +8,7 @@
 
 #include "emit_cell.h"
 #include "exec.h"
+#include "group_hash.h"
 #include "jit.h"
 #include "vm_compile.h"
 #include "knobs.h"
@@ -444,17 +445,18 @@ static DRel HashAggregate(Engine &e, const DRel &tmp, const BoundSelect &s, cons
   for (int g = 0; g < ng; g++) {
     const DCol &c = tmp.cols[g];
     if (c.phys == P_INTERVAL) ThrowError("Not implemented", "GROUP BY on INTERVAL keys is not supported on device");
-    if (c.phys == P_STR && (!c.offsets || !c.chars))
+    // (as the sort requires them: a VARCHAR column without rows has no offsets, one whose strings are all
+    // NULL or '' has no characters; the kernels read `length` bytes, so neither pointer is followed there)
+    if (c.phys == P_STR && tmp.n > 0 && (!c.offsets || (!c.chars && c.chars_len > 0)))
       ThrowError("Internal", "GROUP BY VARCHAR key without materialised strings");
     hk.k[g] = dev::HashKeyCol{c.data, c.validity, c.offsets, c.chars, (int32_t)c.phys};
   }
   const int64_t n = tmp.n;
   // a table of >= 2n entries, at most 2^30 (its scan counts in int32: a 2^31-entry
   // table silently lost every group above 5.4e8 rows); at most one entry per
-  // row is ever claimed, so n <= 2^30 rows always fit
-  int64_t cap = 1024;
-  while (cap < 2 * n && cap < ((int64_t)1 << 30)) cap <<= 1;
-  if (n > ((int64_t)1 << 30)) ThrowError("Not implemented", "GROUP BY input above 2^30 rows on the hash path");
+  // row is ever claimed, so n <= 2^30 rows always fit (group_hash.h)
+  const int64_t cap = GroupCapacity(n);
+  if (n > kGroupMaxRows) ThrowError("Not implemented", "GROUP BY input above 2^30 rows on the hash path");
   auto table = Alloc(e, (size_t)cap * 8);
   HIPCHK(hipMemsetAsync(table->p, 0xFF, (size_t)cap * 8, e.stream));
   auto slot_of = Alloc(e, (size_t)std::max<int64_t>(n, 1) * 4);

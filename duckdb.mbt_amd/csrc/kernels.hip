@@ -54,6 +54,7 @@ __device__ __forceinline__ void clk_stamp(int part) {
 #include "vm_device.h"
 #include "vm_lds.h"
 #include "knobs.h"
+#include "group_hash.h"
 
 namespace mbx {
 namespace dev {
@@ -3297,48 +3298,34 @@ void EmitAggRelation(const EmitDesc &d, hipStream_t s) {
 // ---------------------------------------------------------------------------
 // hash GROUP BY
 // ---------------------------------------------------------------------------
-#define HT_EMPTY 0xFFFFFFFFFFFFFFFFull
-#define HT_ROW_MASK ((1ull << 40) - 1)
-
-__device__ __forceinline__ uint64_t hmix(uint64_t z) {
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
+// The table's arithmetic -- the hash of a key row, the entry packing, the
+// insert walk -- is group_hash.h, shared with the host
+// (tests/plan_harness/group_hash.cpp).
 
 // key value as (up to) 128 bits; floats normalised so -0.0 groups with 0.0
 // and every NaN with every other NaN
 __device__ __forceinline__ void key_bits(const HashKeyCol &c, int64_t r, uint64_t &w0, uint64_t &w1) {
   int64_t lo, hi;
   load_phys(c.data, c.phys, r, lo, hi);
-  if (c.phys == P_F64 || c.phys == P_F32) {
-    double d = __longlong_as_double(lo);
-    if (d == 0.0) d = 0.0;
-    if (d != d) d = __longlong_as_double(0x7FF8000000000000ll);
-    lo = __double_as_longlong(d);
-  }
-  w0 = (uint64_t)lo;
+  w0 = (c.phys == P_F64 || c.phys == P_F32) ? GroupFloatBits((uint64_t)lo) : (uint64_t)lo;
   w1 = (uint64_t)hi;
 }
 
 __device__ uint64_t row_hash(const HashKeys &K, int64_t r) {
-  uint64_t h = 0x9E3779B97F4A7C15ull;
+  uint64_t h = kGroupHashSeed;
   for (int j = 0; j < K.nk; j++) {
     const HashKeyCol &c = K.k[j];
     if (!bit_valid(c.validity, r)) {
-      h = hmix(h ^ 0x5BD1E9955BD1E995ull);
+      h = GroupHashNull(h);
       continue;
     }
     if (c.phys == P_STR) {
-      int64_t b = c.offsets[r], e = c.offsets[r + 1];
-      uint64_t f = 0xCBF29CE484222325ull ^ (uint64_t)(e - b);
-      for (int64_t i = b; i < e; i++) f = (f ^ (uint8_t)c.chars[i]) * 0x100000001B3ull;
-      h = hmix(h ^ f);
+      const int64_t b = c.offsets[r], e = c.offsets[r + 1];
+      h = GroupHashString(h, c.chars + b, e - b);
     } else {
       uint64_t w0, w1;
       key_bits(c, r, w0, w1);
-      h = hmix(h ^ w0);
-      h = hmix(h ^ (w1 + 0x632BE59BD9B4E019ull));
+      h = GroupHashWords(h, w0, w1);
     }
   }
   return h;
@@ -3351,10 +3338,8 @@ __device__ bool rows_equal(const HashKeys &K, int64_t a, int64_t b) {
     if (va != vb) return false;
     if (!va) continue;
     if (c.phys == P_STR) {
-      int64_t ab = c.offsets[a], ae = c.offsets[a + 1], bb = c.offsets[b], be = c.offsets[b + 1];
-      if (ae - ab != be - bb) return false;
-      for (int64_t i = 0; i < ae - ab; i++)
-        if (c.chars[ab + i] != c.chars[bb + i]) return false;
+      const int64_t ab = c.offsets[a], ae = c.offsets[a + 1], bb = c.offsets[b], be = c.offsets[b + 1];
+      if (!GroupStringsEqual(c.chars + ab, ae - ab, c.chars + bb, be - bb)) return false;
     } else {
       uint64_t a0, a1, b0, b1;
       key_bits(c, a, a0, a1);
@@ -3368,35 +3353,23 @@ __device__ bool rows_equal(const HashKeys &K, int64_t a, int64_t b) {
 __global__ __launch_bounds__(256) void hash_insert_kernel(HashKeys K, int64_t n, unsigned long long *table,
                                                           uint64_t mask, int32_t *entry_of, int32_t *err) {
   for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < n; r += (int64_t)gridDim.x * blockDim.x) {
-    const uint64_t h = row_hash(K, r);
-    const uint64_t tag = h >> 40;
-    const unsigned long long mine = (tag << 40) | (uint64_t)r;
-    uint64_t e = h & mask;
-    int32_t got = -1;
-    for (uint64_t probe = 0; probe <= mask; probe++) {
-      unsigned long long cur = __hip_atomic_load(&table[e], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (cur == HT_EMPTY) {
-        unsigned long long prev = atomicCAS(&table[e], HT_EMPTY, mine);
-        if (prev == HT_EMPTY) {
-          got = (int32_t)e;
-          break;
-        }
-        cur = prev;
-      }
-      if ((cur >> 40) == tag && rows_equal(K, (int64_t)(cur & HT_ROW_MASK), r)) {
-        got = (int32_t)e;
-        break;
-      }
-      e = (e + 1) & mask;
-    }
+    const int64_t got = GroupInsert(
+        row_hash(K, r), r, mask,
+        [&](uint64_t e) -> uint64_t {
+          return __hip_atomic_load(&table[e], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        },
+        [&](uint64_t e, uint64_t expected, uint64_t desired) -> uint64_t {
+          return atomicCAS(&table[e], (unsigned long long)expected, (unsigned long long)desired);
+        },
+        [&](int64_t other) { return rows_equal(K, other, r); });
     if (got < 0) atomicCAS(err, 0, E_HASH_FULL);  // cannot happen with cap >= 2n; never loops forever
-    entry_of[r] = got < 0 ? 0 : got;
+    entry_of[r] = got < 0 ? 0 : (int32_t)got;
   }
 }
 
 __global__ void hash_occupancy_kernel(const unsigned long long *table, int64_t cap, int32_t *flag) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < cap; i += (int64_t)gridDim.x * blockDim.x)
-    flag[i] = table[i] != HT_EMPTY;
+    flag[i] = table[i] != kGroupEmpty;
 }
 
 // pos = exclusive scan of the occupancy flags: entry e (occupied) -> group pos[e]
@@ -3405,7 +3378,7 @@ __global__ void hash_groups_kernel(const unsigned long long *table, const int32_
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < cap; i += (int64_t)gridDim.x * blockDim.x) {
     if (flag[i]) {
       gid_of_entry[i] = pos[i];
-      rep_row[pos[i]] = (int64_t)(table[i] & HT_ROW_MASK);
+      rep_row[pos[i]] = GroupEntryRow(table[i]);
     }
     if (i == cap - 1) *ngroups = (int64_t)pos[i] + flag[i];
   }
@@ -3435,7 +3408,7 @@ void CountSlots(const int32_t *slot_of_row, int64_t n, unsigned long long *count
 void HashGroupAssign(const HashKeys &k, int64_t n, unsigned long long *table, int64_t cap, int32_t *slot_of_row,
                      int32_t *gid_of_entry, int64_t *rep_row, unsigned long long *count_star, int64_t *ngroups,
                      int32_t *err, hipStream_t s) {
-  // table must hold HT_EMPTY, count_star zeros (caller); gid_of_entry doubles as scan scratch
+  // table must hold kGroupEmpty, count_star zeros (caller); gid_of_entry doubles as scan scratch
   if (n <= 0) {
     (void)hipMemsetAsync(ngroups, 0, 8, s);
     return;
