@@ -10,6 +10,7 @@
 #include "exec.h"
 #include "group_hash.h"
 #include "jit.h"
+#include "str_minmax.h"
 #include "vm_compile.h"
 #include "knobs.h"
 
@@ -56,16 +57,30 @@ static dev::EmitDesc EmitDescOf(const unsigned long long *cstar, int64_t nslots)
   return D;
 }
 
-// The aggregates' output columns, `rows` rows each, appended to out and
-// entered in D.
+// The columns of the aggregates that have no AggState: MIN / MAX over VARCHAR
+// (StrMinMaxColumns), each the argument column gathered at the winners' rows.
+// has[j]: aggregate j is one, col[j] its column; the emit passes those by.
+struct GatheredAggs {
+  std::vector<DCol> col;
+  std::vector<char> has;
+  bool any = false;
+};
+
+// The aggregates' output columns, `rows` rows each, appended to out in the
+// aggregates' order.  Those the emit writes are entered in D; a gathered one
+// (`gathered`, or none) is put at its place as it is.
 static void EmitAggCols(Engine &e, const BoundSelect &s, int64_t rows, const EmitInOf &in_of, dev::EmitDesc &D,
-                        DRel &out) {
+                        DRel &out, const GatheredAggs *gathered = nullptr) {
   const int na = (int)s.aggs.size();
-  D.nagg = na;
+  D.nagg = 0;
   for (int j = 0; j < na; j++) {
+    if (gathered && gathered->any && gathered->has[j]) {
+      out.cols.push_back(gathered->col[j]);
+      continue;
+    }
     DCol oc = AllocOut(e, s.aggs[j].type, rows, true, false);
     const EmitIn in = in_of(j);
-    D.a[j] = EmitFor(s.aggs[j], in.in_class, in.states, oc, in.wide_minmax);
+    D.a[D.nagg++] = EmitFor(s.aggs[j], in.in_class, in.states, oc, in.wide_minmax);
     out.cols.push_back(oc);
   }
 }
@@ -118,14 +133,16 @@ static ResultTailChoice OneRowTail(const Engine &e, const BoundSelect &s, Result
 // relation says so (DRel::tail), so ToHost has nothing left to copy.
 static DRel EmitOneRow(Engine &e, const BoundSelect &s, const unsigned long long *cstar, const EmitInOf &in_of,
                        const dev::AggPartial *partials = nullptr, int npartials = 0,
-                       const std::function<void(const dev::EmitDesc &)> &launch = nullptr) {
+                       const std::function<void(const dev::EmitDesc &)> &launch = nullptr,
+                       const GatheredAggs *gathered = nullptr) {
   DRel out;
   out.n = 1;
   dev::EmitDesc D = EmitDescOf(cstar, 1);
   D.partials = partials;
   D.npartials = npartials;
-  EmitAggCols(e, s, 1, in_of, D, out);
+  EmitAggCols(e, s, 1, in_of, D, out, gathered);
   auto mark = std::make_shared<ResultTailMark>();
+  // (a gathered column is VARCHAR, which the tail declines: below, D.a and out.cols run in step)
   if (OneRowTail(e, s, *mark).take) {
     mark->serial = e.tail_serial;
     mark->ncols = (size_t)D.nagg;
@@ -273,7 +290,7 @@ DRel EmitGlobalStates(Engine &e, const BoundSelect &s, const unsigned long long 
 // is the caller's: the sites differ in both.
 static DRel KeyedEmit(Engine &e, const BoundSelect &s, const LogicalType &key_type, int64_t kmin, int64_t null_slot,
                       const unsigned long long *cstar, const int32_t *slot_list, const int64_t *n_list, int64_t rows,
-                      const EmitInOf &in_of, dev::EmitDesc &D) {
+                      const EmitInOf &in_of, dev::EmitDesc &D, const GatheredAggs *gathered = nullptr) {
   D = EmitDescOf(cstar, rows);
   D.slot_list = slot_list;
   D.n_list = n_list;
@@ -286,7 +303,7 @@ static DRel KeyedEmit(Engine &e, const BoundSelect &s, const LogicalType &key_ty
   D.key_out = kc.data;
   D.key_valid = (uint32_t *)kc.validity;
   out.cols.push_back(kc);
-  EmitAggCols(e, s, rows, in_of, D, out);
+  EmitAggCols(e, s, rows, in_of, D, out, gathered);
   return out;
 }
 
@@ -419,16 +436,137 @@ static bool WideMinMax(const AggSpec &a, int phys) {
 
 // The generic paths work on tmp = [groups..., agg args...] of the filtered
 // source (FilterProject); arg_idx[j] is aggregate j's column in it, -1 for
-// COUNT(*).  A VARCHAR argument is only ever counted: its offsets stand in.
+// COUNT(*).  A VARCHAR argument is counted through its offsets, or it is the
+// argument of MIN / MAX, which have a path of their own (StrMinMaxColumns) and
+// never come here; the binder refuses every other aggregate over VARCHAR.
 static void ReduceInput(const DCol &c, const AggSpec &a, const void **data, int *phys) {
   *data = c.data;
   *phys = c.phys;
   if (c.phys == P_STR) {
     // COUNT(varchar) only needs the validity: scan the offsets as int64
-    if (a.kind != A_COUNT) ThrowError("Not implemented", "SUM/MIN/MAX/AVG over VARCHAR are not supported on device");
+    if (a.kind != A_COUNT) ThrowError("Internal", "an aggregate over VARCHAR other than COUNT / MIN / MAX reached the device");
     *data = c.offsets;
     *phys = P_I64;
   }
+}
+
+static bool StrMinMaxAgg(const AggSpec &a, const DCol &c) {
+  return c.phys == P_STR && (a.kind == A_MIN || a.kind == A_MAX);
+}
+
+// a VARCHAR column of `rows` NULLs
+static DCol NullStrings(Engine &e, const LogicalType &type, int64_t rows) {
+  DCol d;
+  d.type = type;
+  d.phys = P_STR;
+  auto off = Alloc(e, (size_t)(rows + 1) * 8, true);
+  auto v = Alloc(e, (size_t)Words64(std::max<int64_t>(rows, 1)) * 8, true);
+  d.offsets = (int64_t *)off->p;
+  d.validity = (uint64_t *)v->p;
+  d.owners.push_back(off);
+  d.owners.push_back(v);
+  return d;
+}
+
+// MIN / MAX over the VARCHAR arguments of s (str_minmax.h): for every such
+// aggregate the argument column gathered at its groups' winner rows.  The rows
+// of tmp are in slot slot_of[row] of nslots (slot_of null: one slot, no GROUP
+// BY); output row i is slot slot_list[i] (null: slot i) of nout.  MIN and MAX
+// of one argument share the passes.  What the passes move, per row of tmp:
+// str_minmax_key and str_minmax_live each the offset, the first 8 bytes of the
+// string, the slot and the validity bit; str_minmax_round, per candidate and
+// round, the entry, two offsets, the slot, two chunks and the words.
+static GatheredAggs StrMinMaxColumns(Engine &e, const DRel &tmp, const BoundSelect &s, const std::vector<int> &arg_idx,
+                                     const int32_t *slot_of, int64_t nslots, const int32_t *slot_list, int64_t nout) {
+  const int na = (int)s.aggs.size();
+  GatheredAggs G;
+  G.col.resize(na);
+  G.has.assign(na, 0);
+  for (int j = 0; j < na; j++)
+    if (arg_idx[j] >= 0 && StrMinMaxAgg(s.aggs[j], tmp.cols[arg_idx[j]])) G.has[j] = 1, G.any = true;
+  const int64_t n = tmp.n;
+  for (int j = 0; j < na; j++) {
+    if (!G.has[j] || G.col[j].phys == P_STR) continue;  // (done with an earlier aggregate of the same argument)
+    const int a = arg_idx[j];
+    const DCol &c = tmp.cols[a];
+    int kinds = 0;
+    for (int q = j; q < na; q++)
+      if (G.has[q] && arg_idx[q] == a) kinds |= s.aggs[q].kind == A_MIN ? kStrMinMaxWantMin : kStrMinMaxWantMax;
+    DCol result[SMM_KINDS];
+    if (n <= 0 || nout <= 0 || nslots <= 0) {
+      // no row to offer: nothing is launched (the entry keeps the profile at one
+      // str_minmax_key per argument, with nothing read)
+      ProfScope ps(e, "str_minmax_key", 0, 0);
+      for (int k = 0; k < SMM_KINDS; k++) result[k] = NullStrings(e, c.type, nout);
+    } else {
+      // (a column whose strings are all NULL or '' has offsets and no characters: no byte of it is read)
+      if (!c.offsets || (!c.chars && c.chars_len > 0))
+        ThrowError("Internal", "MIN / MAX over VARCHAR without materialised strings");
+      dev::StrMinMaxRun run;
+      run.col = dev::StrCol{c.offsets, c.chars, c.chars_len, c.validity};
+      run.n = n;
+      run.slot_of = slot_of;
+      run.nslots = nslots;
+      run.kinds = kinds;
+      DevBufPtr words[2] = {Alloc(e, (size_t)nslots * 16), Alloc(e, (size_t)nslots * 16)};
+      auto cand = Alloc(e, (size_t)n * 8);
+      auto ctr = Alloc(e, 16);
+      const double row_bytes = 8 + (double)std::min<int64_t>(c.chars_len, 8 * n) / (double)n + (slot_of ? 4 : 0) +
+                               (c.validity ? 0.125 : 0);
+      {
+        ProfScope ps(e, "str_minmax_key", (double)n * row_bytes, n);
+        dev::StrMinMaxInitWords((uint64_t *)words[0]->p, nslots, 0, 1, e.stream);
+        dev::StrMinMaxKeyPass(run, (uint64_t *)words[0]->p, e.stream);
+      }
+      {
+        ProfScope ps(e, "str_minmax_live", (double)n * row_bytes, n);
+        dev::StrMinMaxLivePass(run, (const uint64_t *)words[0]->p, (uint64_t *)cand->p,
+                               (unsigned long long *)ctr->p, e.stream);
+      }
+      struct Live {
+        uint64_t count, maxlen;
+      };
+      const Live live = ReadDev<Live>(e, ctr->p);
+      const int64_t ncand = (int64_t)std::min<uint64_t>(live.count, (uint64_t)n);
+      // the rounds stop with the longest candidate: no live row has a byte past its chunks
+      const int chunks = StrMinMaxChunks((int64_t)live.maxlen);
+      const int rounds = StrMinMaxRounds(chunks);
+      for (int r = 1; r < rounds; r++) {
+        ProfScope ps(e, "str_minmax_round", (double)ncand * (8 + 16 + (slot_of ? 4 : 0) + 16 + 16), ncand);
+        dev::StrMinMaxInitWords((uint64_t *)words[r & 1]->p, nslots, r, chunks, e.stream);
+        dev::StrMinMaxRoundPass(run, (uint64_t *)cand->p, ncand, r, chunks, (const uint64_t *)words[(r - 1) & 1]->p,
+                                (uint64_t *)words[r & 1]->p, e.stream);
+      }
+      const uint64_t *last = (const uint64_t *)words[(rounds - 1) & 1]->p;
+      DRel arg;
+      arg.n = n;
+      arg.cols.push_back(c);
+      arg.cols[0].validity = nullptr;  // a winner is never NULL; the cells' validity is the rows pass's
+      for (int k = 0; k < SMM_KINDS; k++) {
+        if (!(kinds >> k & 1)) continue;
+        auto rows = Alloc(e, (size_t)nout * 8);
+        auto valid = Alloc(e, (size_t)Words64(nout) * 8);
+        {
+          ProfScope ps(e, "str_minmax_rows", (double)nout * (8 + 8 + (slot_list ? 4 : 0)), nout);
+          dev::StrMinMaxRowsPass(last + (k == SMM_MAX ? nslots : 0), slot_list, nout, nslots, n, (int64_t *)rows->p,
+                                 (uint64_t *)valid->p, e.stream);
+        }
+        // (every row number is in [0, n): a slot without a winner gathers row 0 under a clear bit)
+        DRel g = GatherRel(e, arg, (const int64_t *)rows->p, nout);
+        result[k] = g.cols[0];
+        result[k].validity = (uint64_t *)valid->p;
+        result[k].owners.push_back(valid);
+      }
+      HIPCHK(hipStreamSynchronize(e.stream));  // the run's buffers are released after its last pass
+    }
+    for (int q = j; q < na; q++)
+      if (G.has[q] && arg_idx[q] == a) {
+        G.col[q] = result[s.aggs[q].kind == A_MIN ? SMM_MIN : SMM_MAX];
+        G.col[q].type = s.aggs[q].type;
+        G.col[q].phys = P_STR;
+      }
+  }
+  return G;
 }
 
 // GROUP BY through the device hash table (HashGroupAssign): works for any
@@ -480,6 +618,7 @@ static DRel HashAggregate(Engine &e, const DRel &tmp, const BoundSelect &s, cons
   const unsigned long long *cstar = nullptr;
   DevBufPtr cs;
   // few groups: LDS-privatised reduction keyed by the dense group id
+  // (a MIN / MAX over VARCHAR is a non-integer column to it: the whole select then takes the branch below)
   bool lds = ngroups >= 1 && ngroups <= 1024 &&
              DirectReduceAll(e, slot_of->p, P_I32, 0, ngroups, n, tmp, s, arg_idx, keep, st_of, &cstar);
   if (!lds) {
@@ -487,17 +626,14 @@ static DRel HashAggregate(Engine &e, const DRel &tmp, const BoundSelect &s, cons
     dev::CountSlots((const int32_t *)slot_of->p, n, (unsigned long long *)cs->p, e.stream);
     cstar = (const unsigned long long *)cs->p;
   }
+  GatheredAggs gathered;
+  if (!lds) gathered = StrMinMaxColumns(e, tmp, s, arg_idx, (const int32_t *)slot_of->p, ngroups, nullptr, ngroups);
   for (int j = 0; j < na && !lds; j++) {
-    if (arg_idx[j] < 0) continue;
+    if (arg_idx[j] < 0 || gathered.has[j]) continue;
     const DCol &c = tmp.cols[arg_idx[j]];
-    const void *data = c.data;
-    int phys = c.phys;
-    if (c.phys == P_STR) {
-      if (s.aggs[j].kind != A_COUNT)
-        ThrowError("Not implemented", "SUM/MIN/MAX/AVG over VARCHAR are not supported on device");
-      data = c.offsets;
-      phys = P_I64;
-    }
+    const void *data;
+    int phys;
+    ReduceInput(c, s.aggs[j], &data, &phys);
     states[j] = Alloc(e, (size_t)std::max<int64_t>(ngroups, 1) * sizeof(dev::AggState));
     dev::InitAggStates((dev::AggState *)states[j]->p, ngroups, e.stream);
     wide[j] = WideMinMax(s.aggs[j], phys);
@@ -519,7 +655,7 @@ static DRel HashAggregate(Engine &e, const DRel &tmp, const BoundSelect &s, cons
   dev::EmitDesc D = EmitDescOf(cstar, ngroups);
   EmitAggCols(e, s, ngroups, [&](int j) {
     return EmitIn{st_of[j], arg_idx[j] >= 0 ? ClassOf(tmp.cols[arg_idx[j]].type) : VC_I64, wide[j] != 0};
-  }, D, out);
+  }, D, out, &gathered);
   if (ngroups > 0) dev::EmitAggRelation(D, e.stream);
   HIPCHK(hipStreamSynchronize(e.stream));
   out.n = ngroups;
@@ -1473,8 +1609,9 @@ static DRel GlobalReduce(Engine &e, const DRel &tmp, const BoundSelect &s, const
   unsigned long long cn = (unsigned long long)tmp.n;
   HIPCHK(hipMemcpyAsync(cs->p, &cn, 8, hipMemcpyHostToDevice, e.stream));
   std::vector<char> wide(std::max(na, 1), 0);
+  const GatheredAggs gathered = StrMinMaxColumns(e, tmp, s, arg_idx, nullptr, 1, nullptr, 1);
   for (int j = 0; j < na; j++) {
-    if (arg_idx[j] < 0) continue;
+    if (arg_idx[j] < 0 || gathered.has[j]) continue;
     const DCol &c = tmp.cols[arg_idx[j]];
     const void *data;
     int phys;
@@ -1487,7 +1624,7 @@ static DRel GlobalReduce(Engine &e, const DRel &tmp, const BoundSelect &s, const
   }
   DRel out = EmitOneRow(e, s, (const unsigned long long *)cs->p, [&](int j) {
     return EmitIn{(dev::AggState *)sb->p + j, arg_idx[j] >= 0 ? ClassOf(tmp.cols[arg_idx[j]].type) : VC_I64, wide[j] != 0};
-  });
+  }, nullptr, 0, nullptr, &gathered);
   HIPCHK(hipStreamSynchronize(e.stream));
   return out;
 }
@@ -1541,8 +1678,12 @@ static bool SlotGroupAggregate(Engine &e, const DRel &tmp, const BoundSelect &s,
   const int na = (int)s.aggs.size();
   std::vector<DevBufPtr> states(na);
   std::vector<char> wide(std::max(na, 1), 0);
+  // (which aggregates are gathered is known before their columns are: those need the slot list below)
+  std::vector<char> is_gathered(std::max(na, 1), 0);
+  for (int j = 0; j < na; j++)
+    is_gathered[j] = arg_idx[j] >= 0 && StrMinMaxAgg(s.aggs[j], tmp.cols[arg_idx[j]]);
   for (int j = 0; j < na; j++) {
-    if (arg_idx[j] < 0) continue;
+    if (arg_idx[j] < 0 || is_gathered[j]) continue;
     const DCol &c = tmp.cols[arg_idx[j]];
     const void *data;
     int phys;
@@ -1561,13 +1702,16 @@ static bool SlotGroupAggregate(Engine &e, const DRel &tmp, const BoundSelect &s,
   auto list = Alloc(e, nslots * 4);
   dev::CompactSlots((const unsigned long long *)cs->p, nslots, (int32_t *)list->p, e.d_scratch, e.stream);
   int64_t ngroups = ReadDev<int64_t>(e, e.d_scratch);
+  // (the passes of StrMinMaxColumns use d_scratch for nothing, so the emit still finds the count there)
+  const GatheredAggs gathered =
+      StrMinMaxColumns(e, tmp, s, arg_idx, (const int32_t *)slot_of->p, nslots, (const int32_t *)list->p, ngroups);
   out = KeyedEmit(e, s, s.groups[0]->type, kmin, nslots - 1, (const unsigned long long *)cs->p,
                   (const int32_t *)list->p, e.d_scratch, ngroups,
                   [&](int j) {
                     return EmitIn{states[j] ? (dev::AggState *)states[j]->p : nullptr,
                                   arg_idx[j] >= 0 ? ClassOf(tmp.cols[arg_idx[j]].type) : VC_I64, wide[j] != 0};
                   },
-                  D);
+                  D, &gathered);
   out.n = ngroups;
   // (launched for no groups as well, unlike the LDS form above: kept as it was)
   dev::EmitAggRelation(D, e.stream);
@@ -1625,8 +1769,16 @@ DRel Aggregate(Engine &e, const DRel &src, const BoundSelect &s) {
   // everything else: compact [groups..., agg args...] then reduce
   std::vector<BExprPtr> exprs = s.groups;
   std::vector<int> arg_idx(na, -1);
+  // MIN and MAX of one VARCHAR column read one column of tmp: they share the passes (StrMinMaxColumns)
+  auto str_minmax_of_col = [&](const AggSpec &a) {
+    return (a.kind == A_MIN || a.kind == A_MAX) && a.arg->kind == BExpr::COL && PhysOf(a.arg->type) == P_STR;
+  };
   for (int j = 0; j < na; j++) {
     if (s.aggs[j].kind == A_COUNT_STAR) continue;
+    for (int q = 0; q < j && arg_idx[j] < 0 && str_minmax_of_col(s.aggs[j]); q++)
+      if (s.aggs[q].kind != A_COUNT_STAR && str_minmax_of_col(s.aggs[q]) && s.aggs[q].arg->col == s.aggs[j].arg->col)
+        arg_idx[j] = arg_idx[q];
+    if (arg_idx[j] >= 0) continue;
     arg_idx[j] = (int)exprs.size();
     exprs.push_back(s.aggs[j].arg);
   }

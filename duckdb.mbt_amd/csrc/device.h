@@ -296,6 +296,33 @@ void StrMatch(const StrMatchPlan &plan, const StrCol &a, int64_t n, uint8_t *out
 void StrCompareCols(int op, const StrCol &a, const StrCol &b, int64_t n, uint8_t *out, uint64_t *out_valid,
                     hipStream_t s);
 
+// --- MIN / MAX over VARCHAR (str_kernels.hip; the rounds: str_minmax.h) ---------
+// One run: a string column, the slot of every row (null: all rows are slot 0)
+// and which kinds are wanted (kStrMinMaxWantMin | kStrMinMaxWantMax).  A set of
+// words is 2 * nslots 64-bit words, MIN's then MAX's.
+struct StrMinMaxRun {
+  StrCol col;
+  int64_t n;
+  const int32_t *slot_of;
+  int64_t nslots;
+  int32_t kinds;
+};
+// the words of round r of a run over `chunks` chunks, before any offer
+void StrMinMaxInitWords(uint64_t *words, int64_t nslots, int r, int chunks, hipStream_t s);
+// round 0: every non-NULL row offers its first chunk to its slot's words
+void StrMinMaxKeyPass(const StrMinMaxRun &run, uint64_t *words, hipStream_t s);
+// the rows that are live after round 0 into cand (room for n entries, any
+// order); ctr[0] = their number, ctr[1] = the longest one's length (the call zeroes both)
+void StrMinMaxLivePass(const StrMinMaxRun &run, const uint64_t *words, uint64_t *cand, unsigned long long *ctr,
+                       hipStream_t s);
+// round r >= 1 over the candidates: prev are round r - 1's words, cur (initialised) round r's
+void StrMinMaxRoundPass(const StrMinMaxRun &run, uint64_t *cand, int64_t ncand, int r, int chunks,
+                        const uint64_t *prev, uint64_t *cur, hipStream_t s);
+// rows[i] / bit i of valid (Words64(nout) words, each written whole): the winner of slot slot_list[i]
+// (null: slot i) from one kind's words of the last round (nslots of them), or row 0 and a clear bit
+void StrMinMaxRowsPass(const uint64_t *words, const int32_t *slot_list, int64_t nout, int64_t nslots, int64_t n,
+                       int64_t *rows, uint64_t *valid, hipStream_t s);
+
 // --- ingest / stats ----------------------------------------------------------
 // min/max/null count over rows [0, n) of a fixed-width integer-like column.
 void ColumnStats(const void *col, int phys, const uint64_t *valid, int64_t n, long long *out3, hipStream_t s);

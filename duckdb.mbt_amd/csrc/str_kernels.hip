@@ -20,6 +20,7 @@
 #include <algorithm>
 
 #include "device.h"
+#include "str_minmax.h"
 
 namespace mbx {
 namespace dev {
@@ -252,6 +253,288 @@ void StrCompareCols(int op, const StrCol &a, const StrCol &b, int64_t n, uint8_t
     hipLaunchKernelGGL(and_words_kernel, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, s, a.valid, b.valid, words,
                        out_valid);
   }
+}
+
+// ---- MIN / MAX over VARCHAR (str_minmax.h): rounds of 64-bit atomicMin /
+// atomicMax into one word per group and kind.  str_minmax_key (round 0) and
+// str_minmax_live stream the offsets and the first 8 bytes of every row the way
+// str_match walks a column, a wave step of 256 rows, four consecutive rows per
+// lane, the offsets read once; the later rounds (str_minmax_round) read the
+// candidates that str_minmax_live left.  No kernel waits for another
+// workgroup: every loop below runs over rows or candidates.
+namespace {
+
+constexpr int kMmWaves = 4;
+constexpr int kMmBlocksPerCU = 8;
+
+// words: [0, nslots) MIN's, [nslots, 2 nslots) MAX's
+__global__ void str_minmax_init_kernel(uint64_t *__restrict__ words, int64_t nslots, int r, int chunks) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < 2 * nslots) words[i] = StrMinMaxInitWord(i < nslots ? SMM_MIN : SMM_MAX, r, chunks);
+}
+
+// The offer: a plain look at the word first, the atomic only for a key that
+// would change it (Guideline 12; insert_run of join_kernels.hip does the same
+// for max_run).  The word only moves towards better keys, so a stale look can
+// cost an atomic and never drops one.
+__device__ __forceinline__ void mm_offer(uint64_t *w, bool least, uint64_t key) {
+  const uint64_t cur = __hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (!StrMinMaxImproves(least, key, cur)) return;
+  if (least) atomicMin((unsigned long long *)w, (unsigned long long)key);
+  else atomicMax((unsigned long long *)w, (unsigned long long)key);
+}
+
+__device__ __forceinline__ uint64_t wave_min_u64(uint64_t v) {
+  for (int o = 32; o > 0; o >>= 1) {
+    const uint64_t x = __shfl_xor(v, o);
+    v = x < v ? x : v;
+  }
+  return v;
+}
+__device__ __forceinline__ uint64_t wave_max_u64(uint64_t v) {
+  for (int o = 32; o > 0; o >>= 1) {
+    const uint64_t x = __shfl_xor(v, o);
+    v = x > v ? x : v;
+  }
+  return v;
+}
+
+// the lane's four rows of a step: which are valid rows of the column, their slots
+struct MmRows {
+  uint32_t v4;
+  int32_t g[4];
+};
+__device__ __forceinline__ MmRows mm_rows(const StrMinMaxRun &A, int64_t r0) {
+  MmRows m;
+  m.v4 = 0;
+#pragma unroll
+  for (int k = 0; k < 4; k++) m.g[k] = 0;
+  if (r0 >= A.n) return m;
+  m.v4 = A.col.valid ? (uint32_t)(A.col.valid[r0 >> 6] >> (r0 & 63)) & 0xFu : 0xFu;  // r0 is a multiple of 4
+  if (r0 + 4 > A.n) m.v4 &= (1u << (A.n - r0)) - 1u;
+  if (A.slot_of) {
+    if (r0 + 4 <= A.n && (((uintptr_t)A.slot_of & 15) == 0)) {
+      const int4 q = *(const int4 *)(A.slot_of + r0);
+      m.g[0] = q.x, m.g[1] = q.y, m.g[2] = q.z, m.g[3] = q.w;
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; k++)
+        if (r0 + k < A.n) m.g[k] = A.slot_of[r0 + k];
+    }
+    // a slot outside the words is never followed
+#pragma unroll
+    for (int k = 0; k < 4; k++)
+      if (m.g[k] < 0 || m.g[k] >= A.nslots) m.v4 &= ~(1u << k);
+  }
+  return m;
+}
+
+// Round 0 over every row.  GROUPED: each row offers to its slot's words.
+// Otherwise the lane keeps its least and greatest key over all its steps, the
+// wave reduces them with shuffles and issues one atomic per kind.
+template <bool GROUPED>
+__global__ __launch_bounds__(kMmWaves * 64) void str_minmax_key_kernel(const StrMinMaxRun A,
+                                                                        uint64_t *__restrict__ words) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t nsteps = (A.n + kStepRows - 1) / kStepRows;
+  const uint8_t *const chars = (const uint8_t *)A.col.chars;
+  uint64_t lo = ~0ull, hi = 0;
+  for (int64_t step = (int64_t)blockIdx.x * kMmWaves + wave; step < nsteps; step += (int64_t)gridDim.x * kMmWaves) {
+    const int64_t r0 = step * kStepRows + lane * 4;
+    const Row4 r = load_offsets(A.col.offsets, A.col.chars_len, A.n, r0, step * kStepRows + kStepRows <= A.n, lane);
+    const MmRows m = mm_rows(A, r0);
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      if (!((m.v4 >> k) & 1u)) continue;
+      const uint64_t key = StrMinMaxChunkKey(chars + r.b[k], r.e[k] - r.b[k], A.col.chars_len - r.b[k], 0);
+      if constexpr (GROUPED) {
+        if (A.kinds & kStrMinMaxWantMin) mm_offer(words + m.g[k], true, key);
+        if (A.kinds & kStrMinMaxWantMax) mm_offer(words + A.nslots + m.g[k], false, key);
+      } else {
+        lo = key < lo ? key : lo;
+        hi = key > hi ? key : hi;
+      }
+    }
+  }
+  if constexpr (!GROUPED) {
+    // (a wave without a valid row offers the initial values, which change nothing)
+    lo = wave_min_u64(lo);
+    hi = wave_max_u64(hi);
+    if (lane == 0) {
+      if (A.kinds & kStrMinMaxWantMin) mm_offer(words, true, lo);
+      if (A.kinds & kStrMinMaxWantMax) mm_offer(words + A.nslots, false, hi);
+    }
+  }
+}
+
+// The rows whose round-0 key is their slot's word, for either kind, compacted
+// into cand (room for n entries; the order is whatever the waves' turns at the
+// counter give: no round depends on it).  ctr[0]: their number, ctr[1]: the
+// length of the longest.
+__global__ __launch_bounds__(kMmWaves * 64) void str_minmax_live_kernel(const StrMinMaxRun A,
+                                                                         const uint64_t *__restrict__ words,
+                                                                         uint64_t *__restrict__ cand,
+                                                                         unsigned long long *__restrict__ ctr) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t nsteps = (A.n + kStepRows - 1) / kStepRows;
+  const uint8_t *const chars = (const uint8_t *)A.col.chars;
+  uint64_t maxlen = 0;
+  for (int64_t step = (int64_t)blockIdx.x * kMmWaves + wave; step < nsteps; step += (int64_t)gridDim.x * kMmWaves) {
+    const int64_t r0 = step * kStepRows + lane * 4;
+    const Row4 r = load_offsets(A.col.offsets, A.col.chars_len, A.n, r0, step * kStepRows + kStepRows <= A.n, lane);
+    const MmRows m = mm_rows(A, r0);
+    int live[4];
+    int mine = 0;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      live[k] = 0;
+      if (!((m.v4 >> k) & 1u)) continue;
+      const uint64_t key = StrMinMaxChunkKey(chars + r.b[k], r.e[k] - r.b[k], A.col.chars_len - r.b[k], 0);
+      if ((A.kinds & kStrMinMaxWantMin) && StrMinMaxStaysLive(key, words[m.g[k]])) live[k] |= kStrMinMaxWantMin;
+      if ((A.kinds & kStrMinMaxWantMax) && StrMinMaxStaysLive(key, words[A.nslots + m.g[k]]))
+        live[k] |= kStrMinMaxWantMax;
+      if (live[k]) {
+        mine++;
+        const uint64_t len = (uint64_t)(r.e[k] - r.b[k]);
+        maxlen = len > maxlen ? len : maxlen;
+      }
+    }
+    // the lanes' counts scanned across the wave, one turn at the counter per step
+    int before = mine;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const int x = __shfl_up(before, o);
+      if (lane >= o) before += x;
+    }
+    const int total = __shfl(before, 63);
+    if (total == 0) continue;  // (uniform)
+    before -= mine;
+    unsigned long long base = 0;
+    if (lane == 0) base = atomicAdd(ctr, (unsigned long long)total);
+    base = __shfl(base, 0);
+    int64_t at = (int64_t)base + before;
+#pragma unroll
+    for (int k = 0; k < 4; k++)
+      if (live[k] && at < A.n) cand[at++] = StrMinMaxCand(r0 + k, live[k]);
+  }
+  maxlen = wave_max_u64(maxlen);
+  if (lane == 0 && maxlen > 0) mm_offer((uint64_t *)(ctr + 1), false, maxlen);
+}
+
+// Round r >= 1 over the candidates: a candidate that was live for a kind
+// stays so if its key of round r - 1 is the slot's word of that round (prev),
+// and then offers its key of round r (cur).  Its live bits are written back.
+// Without slots the wave reduces the live lanes' keys first.
+__global__ __launch_bounds__(256) void str_minmax_round_kernel(const StrMinMaxRun A, uint64_t *__restrict__ cand,
+                                                                const int64_t ncand, const int r, const int chunks,
+                                                                const uint64_t *__restrict__ prev,
+                                                                uint64_t *__restrict__ cur) {
+  const int lane = threadIdx.x & 63;
+  const uint8_t *const chars = (const uint8_t *)A.col.chars;
+  const int64_t stride = (int64_t)gridDim.x * 256;
+  // whole waves make the same number of turns (the shuffles below)
+  for (int64_t i0 = (int64_t)blockIdx.x * 256 + (threadIdx.x & ~63); i0 < ncand; i0 += stride) {
+    const int64_t i = i0 + lane;
+    int live = 0, was = 0;
+    uint64_t key = 0;
+    int64_t g = 0;
+    if (i < ncand) {
+      const uint64_t cd = cand[i];
+      const int64_t row = StrMinMaxCandRow(cd);
+      was = StrMinMaxCandLive(cd) & A.kinds;
+      if (row < A.n && was) {
+        g = A.slot_of ? A.slot_of[row] : 0;
+        if (g >= 0 && g < A.nslots) {
+          const int64_t b = min(max(A.col.offsets[row], (int64_t)0), A.col.chars_len);
+          const int64_t e = min(max(A.col.offsets[row + 1], b), A.col.chars_len);
+          const uint64_t pkey = StrMinMaxKey(r - 1, chunks, chars + b, e - b, A.col.chars_len - b, row);
+          key = StrMinMaxKey(r, chunks, chars + b, e - b, A.col.chars_len - b, row);
+          if ((was & kStrMinMaxWantMin) && StrMinMaxStaysLive(pkey, prev[g])) live |= kStrMinMaxWantMin;
+          if ((was & kStrMinMaxWantMax) && StrMinMaxStaysLive(pkey, prev[A.nslots + g])) live |= kStrMinMaxWantMax;
+        }
+      }
+      if (live != StrMinMaxCandLive(cd)) cand[i] = StrMinMaxCand(row, live);
+    }
+#pragma unroll
+    for (int k = 0; k < SMM_KINDS; k++) {
+      const bool on = (live >> k) & 1;
+      const bool least = StrMinMaxTakesLeast(k, r, chunks);
+      uint64_t *const w = cur + (k == SMM_MAX ? A.nslots : 0);
+      if (A.slot_of) {
+        if (on) mm_offer(w + g, least, key);
+      } else {
+        // (a lane that is not live offers the word's initial value: no change)
+        const uint64_t mine = on ? key : StrMinMaxInitWord(k, r, chunks);
+        const uint64_t best = least ? wave_min_u64(mine) : wave_max_u64(mine);
+        if (lane == 0 && (A.kinds >> k & 1)) mm_offer(w, least, best);
+      }
+    }
+  }
+}
+
+// Output row i is slot slot_list[i] (or i): its winner's row number from the
+// last round's words, row 0 and a clear validity bit where the slot has none
+// (or, defensively, a word that is no row of the column).
+__global__ __launch_bounds__(256) void str_minmax_rows_kernel(const uint64_t *__restrict__ words,
+                                                               const int32_t *__restrict__ slot_list,
+                                                               const int64_t nout, const int64_t nslots,
+                                                               const int64_t n, int64_t *__restrict__ rows,
+                                                               uint64_t *__restrict__ valid) {
+  const int lane = threadIdx.x & 63;
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  bool ok = false;
+  if (i < nout) {
+    const int64_t sl = slot_list ? slot_list[i] : i;
+    uint64_t w = kStrMinMaxNoRow;
+    if (sl >= 0 && sl < nslots) w = words[sl];
+    ok = w != kStrMinMaxNoRow && w < (uint64_t)n;
+    rows[i] = ok ? (int64_t)w : 0;
+  }
+  const uint64_t m = __ballot(ok);
+  if (lane == 0 && i < nout) valid[i >> 6] = m;
+}
+
+int mm_grid(int64_t n) {
+  const int64_t nsteps = (n + kStepRows - 1) / kStepRows;
+  const int64_t want = (nsteps + kMmWaves - 1) / kMmWaves;
+  return (int)std::max<int64_t>(1, std::min<int64_t>(want, (int64_t)NumCUs() * kMmBlocksPerCU));
+}
+
+}  // namespace
+
+void StrMinMaxInitWords(uint64_t *words, int64_t nslots, int r, int chunks, hipStream_t s) {
+  if (nslots <= 0) return;
+  hipLaunchKernelGGL(str_minmax_init_kernel, dim3((unsigned)((2 * nslots + 255) / 256)), dim3(256), 0, s, words,
+                     nslots, r, chunks);
+}
+
+void StrMinMaxKeyPass(const StrMinMaxRun &run, uint64_t *words, hipStream_t s) {
+  if (run.n <= 0 || run.nslots <= 0) return;
+  if (run.slot_of)
+    hipLaunchKernelGGL((str_minmax_key_kernel<true>), dim3(mm_grid(run.n)), dim3(kMmWaves * 64), 0, s, run, words);
+  else
+    hipLaunchKernelGGL((str_minmax_key_kernel<false>), dim3(mm_grid(run.n)), dim3(kMmWaves * 64), 0, s, run, words);
+}
+
+void StrMinMaxLivePass(const StrMinMaxRun &run, const uint64_t *words, uint64_t *cand, unsigned long long *ctr,
+                       hipStream_t s) {
+  (void)hipMemsetAsync(ctr, 0, 16, s);
+  if (run.n <= 0 || run.nslots <= 0) return;
+  hipLaunchKernelGGL(str_minmax_live_kernel, dim3(mm_grid(run.n)), dim3(kMmWaves * 64), 0, s, run, words, cand, ctr);
+}
+
+void StrMinMaxRoundPass(const StrMinMaxRun &run, uint64_t *cand, int64_t ncand, int r, int chunks,
+                        const uint64_t *prev, uint64_t *cur, hipStream_t s) {
+  if (ncand <= 0 || run.nslots <= 0 || r < 1) return;
+  const int grid = (int)std::min<int64_t>((ncand + 255) / 256, (int64_t)NumCUs() * 16);
+  hipLaunchKernelGGL(str_minmax_round_kernel, dim3(grid), dim3(256), 0, s, run, cand, ncand, r, chunks, prev, cur);
+}
+
+void StrMinMaxRowsPass(const uint64_t *words, const int32_t *slot_list, int64_t nout, int64_t nslots, int64_t n,
+                       int64_t *rows, uint64_t *valid, hipStream_t s) {
+  if (nout <= 0) return;
+  hipLaunchKernelGGL(str_minmax_rows_kernel, dim3((unsigned)((nout + 255) / 256)), dim3(256), 0, s, words, slot_list,
+                     nout, nslots, n, rows, valid);
 }
 
 }  // namespace dev
